@@ -12,7 +12,11 @@ sequence, their flows in the same batched kernels), every slot a DIFFERENT frame
 resident in 251 GB of HBM (a single frame is latency-bound by PixFlow's raster-order sweeps and leaves most of the chip
 idle; the pole flows' serial chain costs a batch the same whatever it holds: DESIGN.md sections 5 - 7). A step = one batch. Per-GPU work is fixed => "scaling": "weak"; `value` is the aggregate over all ranks. After the timed region
 every context's equirect is downloaded and byte-compared with the render of the same inputs by one context alone
-(`checked`).
+(`checked`, --full).
+
+A plain run (`--gpus N --steps K --warmup W`) does only what `value` needs: it sets up, warms up, times the K steps, writes the
+last step's outputs if `--dump-outputs DIR` is given, and prints the line (`ms_per_step` = milliseconds per timed step). The
+check above and everything below run with `--full`, after the timed region.
 
 Then, one context alone on the GPU (nothing else in flight, so kernel durations are isolated):
   * `roofline`: the dominant kernel of the timed region (the throughput-mode sweep) — algorithmic bytes per launch
@@ -124,6 +128,27 @@ def cpu_baseline_8k(side, top, bottom, rig_path=RIG, flags=None):
 
 
 REF_PROGRAM = os.path.join(ROOT, "oracle", "_ref", "TestRenderStereoPanorama")
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: the pixel sample's size (a whole 8K batch is 4.4 GB)
+
+
+def dump_outputs(path, ctx, slots):
+    """--dump-outputs: what the timed region's last step computed — the equirects of its batch, one per frame slot of the context
+    that ran it — as one fixed, seeded sample of pixels: equirect_sample.npy (slots x n x 3: B, G, R as float32) and
+    equirect_sample_index.npy (n: the flat pixel indices y * width + x, as float64). The same arguments give the same inputs
+    and the same pixels, so that two builds can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    g = ctx.geometry
+    n_px = g.out_height * g.out_width
+    n = min(n_px, DUMP_BYTES // (slots * 3 * 4))
+    idx = np.sort(np.random.default_rng(360).choice(n_px, n, replace=False))
+    sample = np.empty((slots, n, 3), np.float32)
+    for j in range(slots):
+        if slots > 1:
+            ctx.select_frame_slot(j)
+        sample[j] = ctx.download_equirect().reshape(n_px, 3)[idx]
+    np.save(os.path.join(path, "equirect_sample.npy"), sample)
+    np.save(os.path.join(path, "equirect_sample_index.npy"), idx.astype(np.float64))
 
 
 ISP_JSON_NEUTRAL = json.dumps({"CameraIsp": {"bayerPattern": "GBRG"}})  # every other key at CameraIsp's defaults (CameraIsp.h:440-462)
@@ -629,7 +654,7 @@ def main():
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="timed region + check + roofline only (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: timed region + check + roofline only (profiling runs)")
     ap.add_argument("--sharded-child", action="store_true",
                     help="internal (N > 1): the configs[3] leg — one frame sharded over the ranks, the native RCCL exchanges — in "
                          "a process of its own per rank, so that nothing it does can cost the parent's bench line")
@@ -654,7 +679,16 @@ def main():
                          "batch k's pole stage on a second stream beside batch k+1's side stage inside ONE context")
     ap.add_argument("--video-frames", type=int, default=190,
                     help="frames of the configs[4] stream leg (SURVEY 8d: 190, steady state over frames 10-189)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything after the timed region as well: the check of every timed frame, the roofline, the legs "
+                         "(single frame, flow pair, streams, files, CPU baseline, ISP, slots table; N > 1: the sharded frame). "
+                         "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32): a fixed, seeded "
+                         "sample of pixels of every equirect of that batch, and the sampled pixel indices (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` started directly: become the launcher the contract names — one rank per GPU under
@@ -709,7 +743,9 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import rigutil
         cam_size, world_h, pair_size = 128, 256, 100
-        rig_path = rigutil.scaled_rig_json(RIG, "/tmp/bench_dry_run_rig_%d.json" % rank, cam_size / 2048.0)
+        import tempfile
+        rig_path = rigutil.scaled_rig_json(RIG, os.path.join(tempfile.gettempdir(), "bench_dry_run_rig_%d_%d.json" % (os.getpid(), rank)),
+                                           cam_size / 2048.0)
         flags.update(eqr_width=252, eqr_height=126, final_eqr_width=240, final_eqr_height=240)
 
         class _NoCuda:  # the handful of torch.cuda calls of this script
@@ -728,7 +764,7 @@ def main():
     # through the 17 rig cameras on the GPU; frame k = world rotated by 0.2 deg * k, one disc moving 0.5 deg per frame.
     # (The world is the 16384x8192 texture SURVEY 8d names — 2.1 GB of texture + depth on the device while the frames are
     # rendered, freed before the contexts are made; rounds 1-3 used 8192x4096.)
-    n_video = 0 if (args.no_extras or world > 1) else max(args.video_frames, 12)
+    n_video = 0 if (args.no_extras or world > 1 or not args.full) else max(args.video_frames, 12)
     # distinct frames kept in host memory for the stream leg: all of them if the host has room (17 x 12.6 MB each),
     # otherwise a ring walked forwards and backwards (consecutive frames still differ by one step of motion)
     frame_bytes = 17 * cam_size * cam_size * 3
@@ -948,8 +984,8 @@ def main():
     # Untimed set-up before the W warm-up steps: every context renders once (allocations, cached maps), then — only
     # if launches are being held up — frames are rendered until the host-side enqueue time per frame is back to a
     # small multiple of the uncontended one. Observed on shared boxes: for the first seconds after another GPU
-    # process has exited, enqueueing a frame takes ~8x longer and the GPU starves. Bounded at 60 s; not part of the
-    # warm-up or of the timed steps.
+    # process has exited, enqueueing a frame takes ~8x longer and the GPU starves. Bounded at 60 s with --full and at 10 s
+    # in a plain run (whose set-up is kept short); not part of the warm-up or of the timed steps.
     settle = {"batches": 0, "seconds": 0.0}
     if F > 1:
         for _ in range(F):
@@ -960,7 +996,7 @@ def main():
         base_enqueue = time.perf_counter() - t  # one thread, idle GPU queues
         sync(barrier=False)
         t_settle = time.perf_counter()
-        while time.perf_counter() - t_settle < 60.0:
+        while time.perf_counter() - t_settle < (60.0 if args.full else 10.0):
             for k in range(F):
                 enqueue_s[k] = 0.0
             for _ in range(F):
@@ -971,6 +1007,7 @@ def main():
                 break
         settle["seconds"] = time.perf_counter() - t_settle
         sync()  # all ranks settled
+    t_warmup = time.perf_counter()
     for _ in range(args.warmup):
         step()
     drain()
@@ -986,6 +1023,53 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     enqueue_ms_per_frame = 1e3 * sum(enqueue_s) / max(args.steps * S, 1)
+    if args.dump_outputs and rank == 0:  # before anything else runs on the contexts: the last step's batch is still in place
+        dump_outputs(args.dump_outputs, ctxs[(counter[0] - 1) % F], S)
+
+    out = {
+        "metric": "stereo-equirect frames/sec at 8K, 17-cam rig",
+        "value": world * args.steps * S / dt,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * dt / args.steps,
+        "higher_is_better": True,
+        "value_note": "aggregate over INDEPENDENT frames (no predecessor: BASELINE configs[2]); temporally chained streams — every preset of "
+                      "the reference — are the `video_streams_batched` leg, one stream the `video_stream` leg, one frame alone `single_frame` "
+                      "(N GPUs: `sharded_frame`, configs[3], the one leg with RCCL exchanges; all of them with --full)",
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (seeded %dx%d equirect world through the 17-camera rig, 2048x2048 inputs; every in-flight "
+                "context holds a different frame of the stream)" % (2 * world_h, world_h),
+        "config": {"workload": "BASELINE configs[2]: full 17-cam synthetic frame (2048x2048 inputs rendered from the seeded "
+                               "%dx%d equirect world of SURVEY 8d), eqr 8400x4096 -> stereo 8192x8192, "
+                               "top+bottom poles, pixflow_low, sharpening 0.25 (the reference's 8k preset, "
+                               "batch_process_video.py:194-199)" % (2 * world_h, world_h),
+                   "parallelism": "frames: %d GPU(s) x %d contexts x %d slots, no collective" % (world, F, S),
+                   "parallelism_note": "independent frames: each GPU renders whole frames, %d contexts in flight per GPU (one HIP "
+                                       "stream each) of %d frame slots, no data-path collective" % (F, S),
+                   "frames_in_flight": F * S, "contexts": F, "slots_per_context": S, "frames_per_step": S},
+        "host": {"submit_threads": F, "enqueue_ms_per_frame": enqueue_ms_per_frame,
+                 "settle_batches_before_warmup": settle["batches"], "settle_seconds": round(settle["seconds"], 2),
+                 "setup_seconds": round(t_warmup - t_process, 2)},
+    }
+    if dry:
+        out["dry_run"] = "NOT A MEASUREMENT: the library emulated on the CPU at toy sizes (S360_TEST_EMULATED_LIB=1)"
+    if not args.full:  # a plain run: the headline and nothing else (the check, the roofline and the legs are --full's)
+        free_b, total_b = torch.cuda.mem_get_info(dev)
+        out["hbm_used_GB_in_timed_region"] = round((total_b - free_b) / 1e9, 1)
+        if rank == 0:
+            print(json.dumps(out))
+            sys.stdout.flush()
+        for c in ctxs:
+            c.close()
+        for p in pools:
+            p.shutdown()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     # ---- the same region once more without the sharpening pass (SURVEY 8d asks for both; FLAGS_sharpening is a run-time
     # flag): fewer steps, same contexts, same frames. Secondary figure, never `value`.
     steps0 = max(2 * F, min(args.steps, 8))
@@ -1185,43 +1269,15 @@ def main():
     if batched_alone:
         roofline["path_hbm_frac_batch_alone"] = path_bytes * S / (batched_alone["ms_per_batch"] * 1e-3) / 1e9 / HBM_PEAK_GBS
 
-    out = {
-        "metric": "stereo-equirect frames/sec at 8K, 17-cam rig",
-        "value": world * args.steps * S / dt,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": 1e3 * dt / args.steps,
-        "higher_is_better": True,
-        "value_note": "aggregate over INDEPENDENT frames (no predecessor: BASELINE configs[2]); temporally chained streams — every preset of "
-                      "the reference — are the `video_streams_batched` leg, one stream the `video_stream` leg, one frame alone `single_frame` "
-                      "(N GPUs: `sharded_frame`, configs[3], the one leg with RCCL exchanges)",
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (seeded %dx%d equirect world through the 17-camera rig, 2048x2048 inputs; every in-flight "
-                "context holds a different frame of the stream)" % (2 * world_h, world_h),
-        "config": {"workload": "BASELINE configs[2]: full 17-cam synthetic frame (2048x2048 inputs rendered from the seeded "
-                               "%dx%d equirect world of SURVEY 8d), eqr 8400x4096 -> stereo 8192x8192, "
-                               "top+bottom poles, pixflow_low, sharpening 0.25 (the reference's 8k preset, "
-                               "batch_process_video.py:194-199)" % (2 * world_h, world_h),
-                   "parallelism": "frames: %d GPU(s) x %d contexts x %d slots, no collective" % (world, F, S),
-                   "parallelism_note": "independent frames: each GPU renders whole frames, %d contexts in flight per GPU (one HIP "
-                                       "stream each) of %d frame slots, no data-path collective" % (F, S),
-                   "frames_in_flight": F * S, "contexts": F, "slots_per_context": S, "frames_per_step": S},
+    out.update({
         "roofline": roofline,
         "without_sharpening": {"value": world * steps0 * S / dt0, "unit": "frames/s", "steps": steps0,
                                "ms_per_step": 1e3 * dt0 / steps0,
                                "note": "the same contexts and frames with --sharpening 0 (SURVEY 8d: both figures)"},
         "kernel_ms_per_frame_in_flight": {k: round(v[0] / (prof_steps * S), 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])},
-        "host": {"submit_threads": F, "enqueue_ms_per_frame": enqueue_ms_per_frame,
-                 "settle_batches_before_warmup": settle["batches"], "settle_seconds": round(settle["seconds"], 2)},
-    }
+    })
     out.update(checked)
     out["hbm_used_GB_in_timed_region"] = hbm_used_gb
-    if dry:
-        out["dry_run"] = "NOT A MEASUREMENT: the library emulated on the CPU at toy sizes (S360_TEST_EMULATED_LIB=1)"
 
     def emit():
         if rank == 0:

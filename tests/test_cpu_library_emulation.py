@@ -309,7 +309,7 @@ def test_bench_script_dry_run(emu_programs):
     / sharpening / flow-pair / video-stream / end-to-end-files legs, the reference program as the CPU baseline, the ISP leg."""
     import sys
     e = dict(os.environ, S360_TEST_EMULATED_LIB="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--slots", "2", "--inflight", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--slots", "2", "--inflight", "2",
                         "--video-frames", "3"], capture_output=True, text=True, env=e, timeout=3000, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -322,3 +322,30 @@ def test_bench_script_dry_run(emu_programs):
     vb = d["video_streams_batched"]  # batched chained streams, every stream's last frame against the stream rendered alone
     assert "error" not in vb and vb["checked"] is True and vb["checked_streams"] == vb["streams"] == 4 and vb["distinct_last_frames"] >= 3
     assert e2e["single_invocation"]["equals_stream_frame"] is True and e2e["batched_streams"]["first_frame_equals_stream"] is True
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path, emu_programs):
+    """bench.py without --full on the emulated library at toy sizes (S360_TEST_EMULATED_LIB=1: NOT a measurement): the
+    headline line alone, the steps it was asked for, and --dump-outputs writing the last timed step's equirects (one per frame
+    slot) as a seeded pixel sample — the same pixels of the same inputs in a second run."""
+    import sys
+    e = dict(os.environ, S360_TEST_EMULATED_LIB="1")
+    dumps = []
+    for run in range(2):
+        dump = tmp_path / ("outputs%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--slots", "2",
+                            "--inflight", "2", "--dump-outputs", str(dump)], capture_output=True, text=True, env=e, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert "dry_run" in d and "errors" not in d
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert not {"checked", "roofline", "without_sharpening", "single_frame", "video_stream", "cpu_baseline", "isp"} & set(d)
+        sample, index = np.load(dump / "equirect_sample.npy"), np.load(dump / "equirect_sample_index.npy")
+        assert sample.dtype == np.float32 and index.dtype == np.float64
+        assert sample.shape == (2, index.size, 3) and sample.nbytes + index.nbytes <= 64 << 20
+        assert np.all(np.diff(index) > 0) and sample.std() > 0
+        dumps.append((sample, index))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])

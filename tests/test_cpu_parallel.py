@@ -117,7 +117,7 @@ def _check_two_rank_line(r):
     return d
 
 
-BENCH_2 = ["--gpus", "2", "--steps", "1", "--warmup", "0", "--slots", "1", "--inflight", "1", "--video-frames", "14"]
+BENCH_2 = ["--full", "--gpus", "2", "--steps", "1", "--warmup", "0", "--slots", "1", "--inflight", "1", "--video-frames", "14"]
 
 
 def _bench_env(tmp_path):

@@ -10,7 +10,7 @@ for r in $(seq 1 $R); do
   for v in ${VARIANTS:-old new}; do   # a variant "<lib>:<ENV=value>" runs libs360_<lib>.so with that environment variable
     lib=${v%%:*}; envs=""; [ "$lib" != "$v" ] && envs=${v#*:}
     cp surround360_amd/libs360_$lib.so surround360_amd/libs360.so
-    env $envs timeout 600 python bench.py --steps 12 --warmup 6 --no-extras --no-cpu-baseline > $O/${v//[:=]/_}_$r.json 2> $O/${v//[:=]/_}_$r.err
+    env $envs timeout 600 python bench.py --full --steps 12 --warmup 6 --no-extras --no-cpu-baseline > $O/${v//[:=]/_}_$r.json 2> $O/${v//[:=]/_}_$r.err
     python - $O/${v//[:=]/_}_$r.json $v $r <<'P'
 import json, sys
 d = json.load(open(sys.argv[1]))

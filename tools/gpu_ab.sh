@@ -16,7 +16,7 @@ O=gpurun_out/${1:?tag}; mkdir -p $O
     esac
   done
 } > $O/microbench.txt 2>&1
-timeout 600 python bench.py --no-extras --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --no-extras --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 timeout 900 python -m pytest tests/test_gpu_flow.py tests/test_gpu_ops.py tests/test_gpu_frame.py -m gpu -x -q > $O/pytest.log 2>&1
 grep -E "passed|failed|error" $O/pytest.log | tail -2
 cat $O/microbench.txt

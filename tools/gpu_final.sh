@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/${1:?tag}; mkdir -p $O
 timeout 200 python -m pytest tests/test_gpu_ops.py tests/test_gpu_flow.py tests/test_gpu_frame.py -m gpu -x -q > $O/pytest.log 2>&1
 grep -E "passed|failed|error" $O/pytest.log | tail -2
-timeout 420 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 420 python bench.py --full > $O/bench.json 2> $O/bench.err
 python - <<'P' $O/bench.json
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

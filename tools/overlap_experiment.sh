@@ -5,7 +5,7 @@
 # already runs beside another context's kernels (tools/sweep_overlap.py).   usage: bash tools/overlap_experiment.sh <tag>
 TAG=${1:?tag}; O=gpurun_out/$TAG; mkdir -p $O
 cd "$(dirname "$0")/.."
-B="python bench.py --steps 12 --warmup 4 --no-extras --no-cpu-baseline"
+B="python bench.py --full --steps 12 --warmup 4 --no-extras --no-cpu-baseline"
 for inflight in 1 2; do
   $B --inflight $inflight --slots 16 > $O/plain_$inflight.json 2> $O/plain_$inflight.err
   $B --inflight $inflight --slots 16 --pipeline-batches > $O/piped_$inflight.json 2> $O/piped_$inflight.err
@@ -23,9 +23,9 @@ for name in ("plain_1", "piped_1", "plain_2", "piped_2"):
 PY
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 P=/tmp/s360_prof/$TAG; mkdir -p $P
-rocprofv3 --kernel-trace -d $P/kt -o kt -- python bench.py --steps 6 --warmup 2 --no-extras --no-cpu-baseline > $O/kt.log 2>&1
+rocprofv3 --kernel-trace -d $P/kt -o kt -- python bench.py --full --steps 6 --warmup 2 --no-extras --no-cpu-baseline > $O/kt.log 2>&1
 {
-  echo "# rocprofv3 --kernel-trace of: python bench.py --steps 6 --warmup 2 --no-extras --no-cpu-baseline (2 contexts x 22 slots)"
+  echo "# rocprofv3 --kernel-trace of: python bench.py --full --steps 6 --warmup 2 --no-extras --no-cpu-baseline (2 contexts x 22 slots)"
   python tools/sweep_overlap.py $P/kt/kt_results.db "k_sweep_quad<true, 4>" 0.6
   echo
   python tools/sweep_overlap.py $P/kt/kt_results.db "k_sweep_quad<true, 3>" 0.6

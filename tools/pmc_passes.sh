@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 P=/tmp/s360_prof/$TAG; mkdir -p $P
-ISO="python bench.py --inflight 1 --slots $SLOTS --steps 2 --warmup 1 --no-extras --no-cpu-baseline"
+ISO="python bench.py --full --inflight 1 --slots $SLOTS --steps 2 --warmup 1 --no-extras --no-cpu-baseline"
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT -d $P/sq -o sq -- $ISO > $O/sq.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR -d $P/in -o in -- $ISO > $O/in.log 2>&1
 python tools/valu_busy.py $P/sq/sq_results.db > profiles/${TAG}_valu_busy.txt 2>> $O/sq.log

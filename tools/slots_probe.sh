@@ -3,7 +3,7 @@
 # at 2 x {8, 12, 16, 22} slots and temporally chained streams at 2 x {6, 10, 15} slots.   usage: bash tools/slots_probe.sh <tag>
 TAG=${1:?tag}; O=gpurun_out/$TAG; mkdir -p $O
 for s in 8 12 16; do
-  python bench.py --slots $s --steps 16 --warmup 8 --no-extras --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $O/independent_$s.json
+  python bench.py --full --slots $s --steps 16 --warmup 8 --no-extras --no-cpu-baseline 2>/dev/null | grep '^{"metric"' > $O/independent_$s.json
   python - $O/independent_$s.json $s <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); print("independent 2 x %s slots: %.2f frames/s, %s GB, checked %s" % (sys.argv[2], d["value"], d["hbm_used_GB_in_timed_region"], d["checked"]))
