@@ -21,6 +21,7 @@
 // (surround360_render/CMakeLists.txt:33-35), and float op order matters.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <cassert>
 #include <climits>
 #include <cmath>
@@ -29,6 +30,25 @@
 #include <vector>
 
 namespace orc {
+
+// ---------------------------------------------------------------------------
+// Coverage counters (tests only: orc_coverage_reset / orc_coverage_read, tests/oracle_lib.py): how often the oracle's
+// operands reach the edges where a device kernel is most likely to depart from it. Each counter is a relaxed atomic
+// incremented beside the arithmetic it watches, on copies of its operands; no result depends on it.
+enum CoverageCounter {
+  COV_TINY_OPERAND = 0,   // errorFunction / gradient step with an operand in (0, 2^-96): the sweeps' IEEE re-run
+  COV_TIE_REJECTED,       // proposeFlowUpdate: proposalErr == currErr while the proposed flow differs from the current one
+  COV_ALPHA_AT_THRESHOLD, // pixel-levels with alpha0 or alpha1 exactly kUpdateAlphaThreshold (0.9f)
+  COV_MEDIAN_SIGNED_ZEROS,// medianBlur5 windows that hold both +0 and -0
+  COV_SEARCH_TIE,         // adjustInitialFlow: a candidate whose patch error equals the best so far
+  COV_SEARCH_NONFINITE,   // adjustInitialFlow: a non-finite intensity ratio or patch error
+  COV_COUNT
+};
+static inline std::atomic<unsigned long long>* coverageCounters() {
+  static std::atomic<unsigned long long> c[COV_COUNT];
+  return c;
+}
+static inline void coverageHit(int k) { coverageCounters()[k].fetch_add(1, std::memory_order_relaxed); }
 
 // ---------------------------------------------------------------------------
 // Row-major, channel-interleaved image (== continuous cv::Mat).
@@ -587,6 +607,10 @@ static inline ImgF medianBlur5(const ImgF& src) {
         for (int dy = -2; dy <= 2; ++dy)
           for (int dx = -2; dx <= 2; ++dx)
             v[n++] = src.at(clipIdx(y + dy, 0, src.h), clipIdx(x + dx, 0, src.w), k);
+        bool posZero = false, negZero = false;
+        for (int i = 0; i < 25; ++i)
+          if (v[i] == 0.0f) (std::signbit(v[i]) ? negZero : posZero) = true;
+        if (posZero && negZero) coverageHit(COV_MEDIAN_SIGNED_ZEROS);
         std::nth_element(v, v + 12, v + 25);
         dst.at(y, x, k) = v[12];
       }

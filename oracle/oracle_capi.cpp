@@ -141,6 +141,15 @@ void orc_sharpen(uint8_t* bgr, int w, int h, float sharpening) {
   std::memcpy(bgr, i.d.data(), i.bytes());
 }
 
+// ---- coverage counters (cvlite.h: CoverageCounter) ----------------------------
+int orc_coverage_count() { return COV_COUNT; }
+void orc_coverage_reset() {
+  for (int k = 0; k < COV_COUNT; ++k) coverageCounters()[k].store(0, std::memory_order_relaxed);
+}
+void orc_coverage_read(unsigned long long* out /*COV_COUNT*/) {
+  for (int k = 0; k < COV_COUNT; ++k) out[k] = coverageCounters()[k].load(std::memory_order_relaxed);
+}
+
 // ---- PixFlow ---------------------------------------------------------------
 // number of pyramid levels and their sizes for an input of w x h (PixFlow.h:477-491)
 int orc_pixflow_levels(int w, int h, int* lw /*cap 64*/, int* lh) {

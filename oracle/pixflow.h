@@ -116,13 +116,21 @@ struct PixFlow {
                 smoothness * P.smoothnessCoef +
                 P.verticalRegularizationCoef * fabsf(fdy) / float(L.I0->w) +
                 P.horizontalRegularizationCoef * fabsf(fdx) / float(L.I0->h);
+    if (isTiny(dfx * dfx + dfy * dfy) || isTiny((i0x - i1x) * (i0x - i1x) + (i0y - i1y) * (i0y - i1y)) ||
+        isTiny(P.verticalRegularizationCoef * fabsf(fdy)) || isTiny(P.horizontalRegularizationCoef * fabsf(fdx)))
+      coverageHit(COV_TINY_OPERAND);
     return err;
   }
+
+  // coverage only: non-zero and below 2^-96 in magnitude, where the sweeps' fast division / square root re-run the update
+  // with the IEEE expansion (sweep_common.hpp: tiny_key / kTinyBits)
+  static inline bool isTiny(float v) { return v != 0.0f && fabsf(v) < 0x1p-96f; }
 
   // PixFlow.h:415-435
   inline void proposeFlowUpdate(const Level& L, ImgF& flow, float& currErr, int x, int y, float px,
                                 float py) const {
     const float proposalErr = errorFunction(L, x, y, px, py);
+    if (proposalErr == currErr && (px != flow.at(y, x, 0) || py != flow.at(y, x, 1))) coverageHit(COV_TIE_REJECTED);
     if (proposalErr < currErr) {
       flow.at(y, x, 0) = px;
       flow.at(y, x, 1) = py;
@@ -146,6 +154,7 @@ struct PixFlow {
       const float fx0 = flow.at(y, x, 0), fy0 = flow.at(y, x, 1);
       const float ex = errorFunction(L, x, y, fx0 + kGradEpsilon, fy0 + 0.0f);
       const float ey = errorFunction(L, x, y, fx0 + 0.0f, fy0 + kGradEpsilon);
+      if (isTiny(ex - currErr) || isTiny(ey - currErr)) coverageHit(COV_TINY_OPERAND);
       const float gx = (ex - currErr) / kGradEpsilon;
       const float gy = (ey - currErr) / kGradEpsilon;
       flow.at(y, x, 0) = fx0 - P.gradientStepSize * gx;
@@ -204,6 +213,7 @@ struct PixFlow {
         sumRhs += a * I1.at(y, x);
       }
     const float ratio = sumLhs / sumRhs;
+    if (!std::isfinite(ratio)) coverageHit(COV_SEARCH_NONFINITE);
     ImgF I1eq(I1.w, I1.h, 1);
     for (size_t i = 0; i < I1.d.size(); ++i) I1eq.d[i] = I1.d[i] * ratio;
     // computeSearchBox, PixFlow.h:279-296
@@ -223,12 +233,15 @@ struct PixFlow {
         if (alpha0.at(i0y, i0x) > kUpdateAlphaThreshold) {
           const float kFraction = 0.8f;
           float errorBest = kFraction * computePatchError(I0, alpha0, i0x, i0y, I1eq, alpha1, i0x, i0y);
+          if (!std::isfinite(errorBest)) coverageHit(COV_SEARCH_NONFINITE);
           int i1xBest = i0x, i1yBest = i0y;
           for (int dy = by; dy < by + bh; ++dy)
             for (int dx = bx; dx < bx + bw; ++dx) {
               const int i1x = i0x + dx, i1y = i0y + dy;
               if (0 <= i1x && i1x < I1.w && 0 <= i1y && i1y < I1.h) {
                 const float error = computePatchError(I0, alpha0, i0x, i0y, I1eq, alpha1, i1x, i1y);
+                if (!std::isfinite(error)) coverageHit(COV_SEARCH_NONFINITE);
+                if (error == errorBest && (i1x != i1xBest || i1y != i1yBest)) coverageHit(COV_SEARCH_TIE);
                 if (errorBest > error) { errorBest = error; i1xBest = i1x; i1yBest = i1y; }
               }
             }
@@ -252,6 +265,9 @@ struct PixFlow {
     }
     L.blurredFlow = gaussianBlurF32(flow, kBlurredFlowKernelWidth, kBlurredFlowSigma);
     const int w = I0.w, h = I0.h;
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x)
+        if (alpha0.at(y, x) == kUpdateAlphaThreshold || alpha1.at(y, x) == kUpdateAlphaThreshold) coverageHit(COV_ALPHA_AT_THRESHOLD);
     for (int y = 0; y < h; ++y)
       for (int x = 0; x < w; ++x) sweepPixel(L, flow, x, y, +1);
     flow = medianBlur5(flow);

@@ -129,15 +129,17 @@ def _camera_rays(cam, res):
     return unit @ R  # R^T * unit per pixel
 
 
-def rig_frame(rig_json_path, size=2048, world_h=2048, seed=360, yaw_deg=0.0, return_all=False):
+def rig_frame(rig_json_path, size=2048, world_h=2048, seed=360, yaw_deg=0.0, return_all=False, world=None, nearest=False):
     """Render every camera of the rig from the seeded world. Returns (list of side BGR images in
     rigSideOnly order, top BGR, bottom BGR). One fixed-point iteration places each ray's hit
     point at the world depth seen from the rig centre, which gives consistent parallax between
     adjacent cameras. return_all=True also returns the dict {camera id: image} of every camera of the rig (the
-    secondary bottom camera of pole removal is not one of the three standard outputs)."""
+    secondary bottom camera of pole removal is not one of the three standard outputs).
+    world=(texture 2h x h BGR, depth h x 2h in cm) replaces the seeded world (world_h / seed are then unused);
+    nearest=True samples it nearest-neighbour instead of bilinearly, so that hard edges stay hard."""
     with open(rig_json_path) as f:
         cams = json.load(f)["cameras"]
-    tex, depth = world_texture(world_h, seed)
+    tex, depth = world if world is not None else world_texture(world_h, seed)
     H, W = tex.shape[:2]
     imgs = {}
     for cam in cams:
@@ -156,6 +158,9 @@ def rig_frame(rig_json_path, size=2048, world_h=2048, seed=360, yaw_deg=0.0, ret
             c = (org * org).sum() - d.astype(np.float64) ** 2
             t = -b + np.sqrt(np.maximum(b * b - c, 0))
             p = org + rays * t[..., None]
+        if nearest:
+            imgs[cam["id"]] = tex[np.clip(v.astype(np.int32), 0, H - 1), np.mod(u.astype(np.int32), W)]
+            continue
         imgs[cam["id"]] = np.clip(_bilinear_sample(tex, u.astype(np.float32), v.astype(np.float32), wrap_x=True),
                                   0, 255).astype(np.uint8)
     side = [imgs[c["id"]] for c in cams if "side" in c.get("group", "")]

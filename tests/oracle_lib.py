@@ -218,8 +218,39 @@ def sharpen(bgr, amount):
     return b
 
 
+# ---- coverage counters (oracle/cvlite.h: CoverageCounter, in that order) -----------------------------------------
+COVERAGE_NAMES = ("tiny_operand", "tie_rejected", "alpha_at_threshold", "median_signed_zeros", "search_tie",
+                  "search_nonfinite")
+
+
+def coverage_reset():
+    lib().orc_coverage_reset()
+
+
+def coverage_read():
+    """{name: count} since the last coverage_reset(); counts every oracle call of this process, all threads."""
+    n = lib().orc_coverage_count()
+    assert n == len(COVERAGE_NAMES), "oracle/cvlite.h has %d coverage counters" % n
+    out = (C.c_ulonglong * n)()
+    lib().orc_coverage_read(out)
+    return dict(zip(COVERAGE_NAMES, list(out)))
+
+
+class coverage:
+    """with oracle_lib.coverage() as cov: ... — cov.counts holds the counters of the oracle calls made inside the block."""
+
+    def __enter__(self):
+        coverage_reset()
+        self.counts = {}
+        return self
+
+    def __exit__(self, *exc):
+        self.counts = coverage_read()
+        return False
+
+
 # ---- PixFlow --------------------------------------------------------------------
-HINT = {"UNKNOWN": 0, "RIGHT": 1, "DOWN": 2, "LEFT": 3, "UP": 4}
+HINT ={"UNKNOWN": 0, "RIGHT": 1, "DOWN": 2, "LEFT": 3, "UP": 4}
 
 
 def pixflow_levels(w, h):

@@ -73,9 +73,11 @@ def test_unknown_algorithm_raises(ctx):
         ctx.compute_optical_flow(i0, i1, "no_such_flow")
 
 
-def test_identical_images_near_zero_flow(ctx):
+def test_identical_images_near_zero_flow(ctx, oracle):
     i0, _ = synth.flow_pair(192, 192, seed=9)
     f = ctx.compute_optical_flow(i0, i0)
+    want = oracle.compute_optical_flow(i0, i0)
+    assert np.array_equal(bits(f), bits(want)), "max abs diff %g" % np.abs(f - want).max()
     assert np.abs(f).max() < 0.5
 
 
