@@ -168,6 +168,24 @@ int s360_spherical_warp_map(s360_ctx* ctx, float* map_out, int dst_w, int dst_h,
 int s360_combine_lazy_novel_views(s360_ctx* ctx, const uint8_t* image_l, const uint8_t* image_r,
                                   const float* flow_l_to_r, const float* flow_r_to_l, uint8_t* chunk_l,
                                   uint8_t* chunk_r);
+/* NovelViewGeneratorLazyFlow::generateNovelView (SR/optical_flow/NovelView.cpp:156-172) — the direct operator: the
+ * view at shift_from_left = t between two images of one size, given their flows. from_l = imageL warped through
+ * flowRtoL * t and from_r = imageR through flowLtoR * (1 - t) (generateNovelViewSimpleCvRemap, NovelView.cpp:20-44:
+ * remap INTER_CUBIC, constant border), merged = combineNovelViews of the two (NovelView.cpp:46-99). One call renders n
+ * shifts of the pair in one launch; n = 1 is the reference's call. image_l/r: w x h BGRA; flows: w x h x 2 floats;
+ * shifts: n doubles (the reference's type); out_merged, out_from_l, out_from_r: n consecutive w x h BGRA images.
+ * out_from_l / out_from_r may be NULL: the warped images are then never written. */
+int s360_generate_novel_views(s360_ctx* ctx, const uint8_t* image_l, const uint8_t* image_r, const float* flow_l_to_r,
+                              const float* flow_r_to_l, int w, int h, const double* shifts, int n, uint8_t* out_merged,
+                              uint8_t* out_from_l, uint8_t* out_from_r);
+/* NovelViewGeneratorAsymmetricFlow::prepare (NovelView.cpp:270-299) followed by generateNovelView for n shifts — what
+ * TestOpticalFlow does with a pair (SR/test/TestOpticalFlow.cpp:68-106): flowLtoR = flow(L, R, LEFT), flowRtoL =
+ * flow(R, L, RIGHT), no previous-frame terms. The images are uploaded once and the flows stay on the device between the
+ * two steps; out_flow_l_to_r / out_flow_r_to_l (w x h x 2 floats) are optional downloads and may be NULL, as may
+ * out_from_l / out_from_r. Unknown algorithm names: S360_ERR_UNKNOWN_ALG. */
+int s360_interpolate_views(s360_ctx* ctx, const char* alg, const uint8_t* image_l, const uint8_t* image_r, int w, int h,
+                           const double* shifts, int n, uint8_t* out_merged, uint8_t* out_from_l, uint8_t* out_from_r,
+                           float* out_flow_l_to_r, float* out_flow_r_to_l);
 /* flattenLayersDeghostPreferBase (SR/util/CvUtil.cpp:224-260). BGRA in, BGRA out. */
 int s360_flatten_layers_deghost_prefer_base(s360_ctx* ctx, const uint8_t* bottom_layer, const uint8_t* top_layer, int w,
                                             int h, uint8_t* out);

@@ -71,7 +71,7 @@ SYMBOLS = [
     "s360_pole_ramp", "s360_create",
     "s360_destroy", "s360_get_geometry", "s360_stream", "s360_synchronize", "s360_set_sharpening", "s360_compute_optical_flow",
     "s360_compute_optical_flow_batch", "s360_bicubic_remap_to_spherical", "s360_spherical_warp_map",
-    "s360_combine_lazy_novel_views", "s360_flatten_layers_deghost_prefer_base", "s360_offset_horizontal_wrap",
+    "s360_combine_lazy_novel_views", "s360_generate_novel_views", "s360_interpolate_views", "s360_flatten_layers_deghost_prefer_base", "s360_offset_horizontal_wrap",
     "s360_feather_alpha_channel", "s360_pole_to_side_flow", "s360_sharpen", "s360_frame_upload_side",
     "s360_frame_upload_top", "s360_frame_upload_bottom", "s360_frame_upload_pole_removal", "s360_frame_set_prev_pole_removal", "s360_frame_render", "s360_frame_render_pairs",
     "s360_frame_set_prev_side", "s360_frame_set_prev_pole", "s360_frame_strip_ptr", "s360_frame_finish", "s360_frame_download_equirect", "s360_frame_equirect_dev",

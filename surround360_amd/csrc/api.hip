@@ -519,6 +519,70 @@ int s360_combine_lazy_novel_views(s360_ctx* c, const uint8_t* image_l, const uin
     d2h(c, chunk_r, c->op_c.as<uint8_t>() + sn * 4, sn * 4);
   });
 }
+// generateNovelView for n shifts of the pair whose images are op_a[0], op_a[1] and whose flows are op_b[0] (LtoR), op_b[1] (RtoL)
+static void morph_views_resident(s360_ctx* c, int w, int h, const double* shifts, int n, uint8_t* out_merged, uint8_t* out_from_l,
+                                 uint8_t* out_from_r) {
+  FrameState& F = frame_state(c);
+  const size_t px = (size_t)w * h, V = n;
+  c->op_c.ensure(V * px * 4 * (1 + (out_from_l ? 1 : 0) + (out_from_r ? 1 : 0)));
+  c->op_d.ensure(V * sizeof(double));
+  h2d(c, c->op_d.p, shifts, V * sizeof(double));
+  uchar4* merged = c->op_c.as<uchar4>();
+  uchar4* fromL = out_from_l ? merged + V * px : nullptr;
+  uchar4* fromR = out_from_r ? merged + V * px * (out_from_l ? 2 : 1) : nullptr;
+  // (developer switch S360_MORPH_VPB: views per grid.z slice, for tools/morph_time.py's comparison of the two mappings; same bytes either way)
+  const char* e = std::getenv("S360_MORPH_VPB");
+  {
+    ProfScope ps(c->prof, "morph_views");
+    launch_morph_views(c->st, c->op_a.as<uchar4>(), c->op_a.as<uchar4>() + px, c->op_b.as<float2>(), c->op_b.as<float2>() + px, w, h,
+                       c->op_d.as<double>(), n, merged, fromL, fromR, F.tab.dev, e ? std::atoi(e) : 0);
+  }
+  d2h(c, out_merged, merged, V * px * 4);
+  if (fromL) d2h(c, out_from_l, fromL, V * px * 4);
+  if (fromR) d2h(c, out_from_r, fromR, V * px * 4);
+}
+int s360_generate_novel_views(s360_ctx* c, const uint8_t* image_l, const uint8_t* image_r, const float* flow_l_to_r,
+                              const float* flow_r_to_l, int w, int h, const double* shifts, int n, uint8_t* out_merged,
+                              uint8_t* out_from_l, uint8_t* out_from_r) {
+  return guard(c, [&] {
+    need(c && image_l && image_r && flow_l_to_r && flow_r_to_l && shifts && out_merged, "null argument");
+    need(w > 0 && h > 0, "image size must be positive");
+    need(n >= 1, "at least one shift is required");
+    const size_t px = (size_t)w * h;
+    c->op_a.ensure(2 * px * 4);
+    c->op_b.ensure(2 * px * sizeof(float2));
+    h2d(c, c->op_a.p, image_l, px * 4);
+    h2d(c, c->op_a.as<uint8_t>() + px * 4, image_r, px * 4);
+    h2d(c, c->op_b.p, flow_l_to_r, px * sizeof(float2));
+    h2d(c, c->op_b.as<float2>() + px, flow_r_to_l, px * sizeof(float2));
+    morph_views_resident(c, w, h, shifts, n, out_merged, out_from_l, out_from_r);
+  });
+}
+int s360_interpolate_views(s360_ctx* c, const char* alg, const uint8_t* image_l, const uint8_t* image_r, int w, int h,
+                           const double* shifts, int n, uint8_t* out_merged, uint8_t* out_from_l, uint8_t* out_from_r,
+                           float* out_flow_l_to_r, float* out_flow_r_to_l) {
+  return guard(c, [&] {
+    need(c && alg && image_l && image_r && shifts && out_merged, "null argument");
+    need(w >= 4 && h >= 4, "image too small: the reference's bilinear taps need a 2x2 image after the x0.5 entry downscale (PixFlow.h:457-475)");
+    need(n >= 1, "at least one shift is required");
+    const PixFlowConsts pc = pixflow_consts_by_name(alg);
+    const size_t px = (size_t)w * h;
+    c->op_a.ensure(2 * px * 4);
+    c->op_b.ensure(2 * px * sizeof(float2));
+    h2d(c, c->op_a.p, image_l, px * 4);
+    h2d(c, c->op_a.as<uint8_t>() + px * 4, image_r, px * 4);
+    // NovelViewGeneratorAsymmetricFlow::prepare (NovelView.cpp:270-299): (L, R, LEFT) then (R, L, RIGHT), no previous frame
+    for (int d = 0; d < 2; ++d) {
+      FlowBatch fb;
+      fb.add_images(c->op_a.as<uchar4>(), 2, px);
+      fb.add_flow(d, 1 - d, c->op_b.as<float2>() + px * d);
+      c->flow->compute(c->st, pc, fb, w, h, d == 0 ? S360_HINT_LEFT : S360_HINT_RIGHT);
+    }
+    morph_views_resident(c, w, h, shifts, n, out_merged, out_from_l, out_from_r);
+    if (out_flow_l_to_r) d2h(c, out_flow_l_to_r, c->op_b.p, px * sizeof(float2));
+    if (out_flow_r_to_l) d2h(c, out_flow_r_to_l, c->op_b.as<float2>() + px, px * sizeof(float2));
+  });
+}
 int s360_flatten_layers_deghost_prefer_base(s360_ctx* c, const uint8_t* bottom_layer, const uint8_t* top_layer, int w,
                                             int h, uint8_t* out) {
   return guard(c, [&] {

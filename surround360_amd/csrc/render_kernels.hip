@@ -733,6 +733,68 @@ __global__ __launch_bounds__(NV_TW* NV_TH) void k_novel_view(const uchar4* __res
 }
 
 // ------------------------------------------------------------------------------------------
+// combineNovelViews (NovelView.cpp:46-99), the direct operator's blend. Against combine_lazy: blendL / blendR are the
+// caller's (1 - t, t) and not the alpha ratio, the alphas go INSIDE the exponent, kFlowMagCoef is 100, every visible
+// result has alpha 255, and the magnitudes cross over: |flowRtoL| weighs the left exponent, |flowLtoR| the right one.
+__device__ __forceinline__ uchar4 combine_novel(uchar4 cL, float blendL, uchar4 cR, float blendR, float flowMagLR,
+                                                float flowMagRL, const DevTables& T) {
+  if (cL.w == 0 && cR.w == 0) return make_uchar4(0, 0, 0, 0);
+  if (cR.w == 0) return make_uchar4(cL.x, cL.y, cL.z, 255);
+  if (cL.w == 0) return make_uchar4(cR.x, cR.y, cR.z, 255);
+  const int sdiff = abs((int)cL.x - (int)cR.x) + abs((int)cL.y - (int)cR.y) + abs((int)cL.z - (int)cR.z);
+  const float deghostCoef = T.tanh10[sdiff];
+  const float alphaL = (float)cL.w / 255.0f, alphaR = (float)cR.w / 255.0f;
+  // float * float * float, then double: kSoftmaxSharpness * blendL * alphaL * (1.0 + kFlowMagCoef * flowMagRL)
+  const double expL = exp((double)(10.0f * blendL * alphaL) * (1.0 + (double)(100.0f * flowMagRL)));
+  const double expR = exp((double)(10.0f * blendR * alphaR) * (1.0 + (double)(100.0f * flowMagLR)));
+  const double sumExp = expL + expR + 0.00001;
+  const float softmaxL = (float)(expL / sumExp);
+  const float softmaxR = (float)(expR / sumExp);
+  const float wL = lerpf(blendL, softmaxL, deghostCoef), wR = lerpf(blendR, softmaxR, deghostCoef);
+  return make_uchar4((unsigned char)trunc_u8((float)cL.x * wL + (float)cR.x * wR),
+                     (unsigned char)trunc_u8((float)cL.y * wL + (float)cR.y * wR),
+                     (unsigned char)trunc_u8((float)cL.z * wL + (float)cR.z * wR), 255);
+}
+// generateNovelView (NovelView.cpp:20-44, 156-172) for n shifts of one pair: generateNovelViewSimpleCvRemap of imageL
+// through flowRtoL * t and of imageR through flowLtoR * (1 - t), then combineNovelViews, per output pixel — the two warped
+// images exist only in registers unless the caller asked for them (fromL / fromR non-null). The flows are read at the
+// OUTPUT pixel. t is the reference's double: the warp coordinate is float(double(x) + double(f.x) * t) and 1.0 - t is
+// formed in double; blendL / blendR are those doubles narrowed at combineNovelViews' float parameters.
+// A workgroup renders a 64 x 4 tile (k_novel_view's shape and XCD-aware order) for `vpb` consecutive views: blockIdx.z
+// picks the group of views, the views of a group are a loop in the thread, which reads its two flow vectors and forms the
+// two magnitudes once and finds the image neighbourhoods of the previous view in L1 / L2.
+// vpb = n ("shifts as a loop") is what ships: 11 views of a 2048 x 2048 pair take 0.658 ms merged only / 0.670 ms with both
+// warped images written, against 0.772 / 0.782 ms with vpb = 1 ("shifts as grid.z", eleven times the flow reads and eleven
+// passes over the images); one view takes 0.079 ms, 0.19 of HBM on its algorithmic bytes
+// (profiles/novel_view_morph.txt, tools/morph_time.py). Bound like k_novel_view by the 2 x 64 integer multiply-adds per pixel.
+__global__ __launch_bounds__(NV_TW* NV_TH) void k_morph_views(const uchar4* __restrict__ imgL, const uchar4* __restrict__ imgR,
+                                                              const float2* __restrict__ flowLtoR,
+                                                              const float2* __restrict__ flowRtoL, int w, int h,
+                                                              const double* __restrict__ shifts, int n, int vpb,
+                                                              uchar4* __restrict__ merged, uchar4* __restrict__ fromL,
+                                                              uchar4* __restrict__ fromR, DevTables T) {
+  const TileId tile = xcd_tile();
+  const int x = tile.x * NV_TW + (threadIdx.x & (NV_TW - 1)), y = tile.y * NV_TH + (threadIdx.x >> 6);
+  if (x >= w || y >= h) return;
+  const size_t px = (size_t)y * w + x, isz = (size_t)w * h;
+  const float2 fLR = flowLtoR[px], fRL = flowRtoL[px];
+  const float flowMagLR = sqrtf(fLR.x * fLR.x + fLR.y * fLR.y) / (float)w;
+  const float flowMagRL = sqrtf(fRL.x * fRL.x + fRL.y * fRL.y) / (float)w;
+  const int v0 = (int)tile.z * vpb, v1 = min(n, v0 + vpb);
+  for (int v = v0; v < v1; ++v) {
+    const double t = shifts[v], u = 1.0 - t;
+    const uchar4 cL = remap_cubic_u8c4_at(imgL, w, h, (float)((double)x + (double)fRL.x * t),
+                                          (float)((double)y + (double)fRL.y * t), T.bicubic_i);
+    const uchar4 cR = remap_cubic_u8c4_at(imgR, w, h, (float)((double)x + (double)fLR.x * u),
+                                          (float)((double)y + (double)fLR.y * u), T.bicubic_i);
+    const size_t o = isz * v + px;
+    merged[o] = combine_novel(cL, (float)u, cR, (float)t, flowMagLR, flowMagRL, T);
+    if (fromL) fromL[o] = cL;
+    if (fromR) fromR[o] = cR;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // offsetHorizontalWrap's source column (CvUtil.cpp:93-115): nearest remap with BORDER_WRAP
 __device__ __forceinline__ int wrap_src_col(int x, float offset, int W) {
   float srcX = (float)x - offset;
@@ -1721,6 +1783,15 @@ void launch_novel_view(hipStream_t st, const uchar4* overlaps, const float2* flo
   if (p1 <= p0) return;
   hipLaunchKernelGGL(k_novel_view, dim3(cdiv(nv.stripW, NV_TW), cdiv(nv.camH, NV_TH), 2 * (p1 - p0)), dim3(NV_TW * NV_TH), 0, st,
                      overlaps, flows, strips, nv, p0, T);
+}
+void launch_morph_views(hipStream_t st, const uchar4* imgL, const uchar4* imgR, const float2* flowLtoR, const float2* flowRtoL,
+                        int w, int h, const double* shifts, int n, uchar4* merged, uchar4* fromL, uchar4* fromR,
+                        const DevTables& T, int views_per_block) {
+  if (n <= 0) return;
+  int vpb = views_per_block > 0 ? min(views_per_block, n) : n;
+  if (cdiv(n, vpb) > 65535u) vpb = (int)cdiv(n, 65535);  // grid.z limit
+  hipLaunchKernelGGL(k_morph_views, dim3(cdiv(w, NV_TW), cdiv(h, NV_TH), cdiv(n, vpb)), dim3(NV_TW * NV_TH), 0, st, imgL, imgR,
+                     flowLtoR, flowRtoL, w, h, shifts, n, vpb, merged, fromL, fromR, T);
 }
 void launch_assemble_pano(hipStream_t st, const uchar4* strips_eye, int P, int camH, int stripW, float offset,
                           uchar4* pano, int eqrW, int eqrH) {

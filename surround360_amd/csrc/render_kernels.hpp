@@ -65,6 +65,12 @@ void launch_crop_overlaps(hipStream_t st, const uchar4* proj, int camW, int camH
 // fused renderLazyNovelView x4 + combineLazyViews x2 for pairs [p0,p1): strips[eye][pair][camH][stripW]
 void launch_novel_view(hipStream_t st, const uchar4* overlaps, const float2* flows /*[2n]: LtoR[n], RtoL[n]*/,
                        uchar4* strips, const NovelViewParams& nv, int p0, int p1, const DevTables& T);
+// generateNovelView (NovelView.cpp:156-172) for n shifts (device doubles) of one pair: merged / fromL / fromR are n
+// consecutive w*h images, fromL / fromR nullable. views_per_block: 0 or >= n = all views as a loop in the
+// workgroup (what ships), 1 = one view per grid.z slice (measured slower; tools/morph_time.py compares the two)
+void launch_morph_views(hipStream_t st, const uchar4* imgL, const uchar4* imgR, const float2* flowLtoR, const float2* flowRtoL,
+                        int w, int h, const double* shifts, int n, uchar4* merged, uchar4* fromL, uchar4* fromR,
+                        const DevTables& T, int views_per_block = 0);
 // stackHorizontal + offsetHorizontalWrap + padToheight (TRSP:380-384, 806-807) for one eye
 void launch_assemble_pano(hipStream_t st, const uchar4* strips_eye, int P, int camH, int stripW, float offset,
                           uchar4* pano, int eqrW, int eqrH);

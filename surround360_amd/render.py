@@ -192,6 +192,38 @@ class Context:
             _p(np.ascontiguousarray(flow_r_to_l, np.float32)), _p(cl), _p(cr)))
         return cl, cr
 
+    def generate_novel_views(self, img_l, img_r, flow_l_to_r, flow_r_to_l, shifts, want_sides=False):
+        """generateNovelView (NovelView.cpp:156-172) for every shift_from_left in `shifts`: merged views [n][h][w][4], and with
+        want_sides also the two warped images (merged, from_l, from_r)."""
+        il, ir = _u8(img_l), _u8(img_r)
+        h, w = il.shape[:2]
+        sh = np.ascontiguousarray(np.atleast_1d(shifts), np.float64)
+        n = sh.shape[0]
+        merged = np.empty((n, h, w, 4), np.uint8)
+        fl, fr = (np.empty_like(merged), np.empty_like(merged)) if want_sides else (None, None)
+        self._ck(lib().s360_generate_novel_views(
+            self.h, _p(il), _p(ir), _p(np.ascontiguousarray(flow_l_to_r, np.float32)),
+            _p(np.ascontiguousarray(flow_r_to_l, np.float32)), w, h, _p(sh), n, _p(merged), _p(fl), _p(fr)))
+        return (merged, fl, fr) if want_sides else merged
+
+    def interpolate_views(self, img_l, img_r, shifts, alg="pixflow_low", want_sides=False, want_flows=False):
+        """NovelViewGeneratorAsymmetricFlow::prepare + generateNovelView per shift, flows kept on the device in between.
+        Returns merged, then (from_l, from_r) with want_sides, then (flow_l_to_r, flow_r_to_l) with want_flows."""
+        il, ir = _u8(img_l), _u8(img_r)
+        h, w = il.shape[:2]
+        sh = np.ascontiguousarray(np.atleast_1d(shifts), np.float64)
+        n = sh.shape[0]
+        merged = np.empty((n, h, w, 4), np.uint8)
+        fl, fr = (np.empty_like(merged), np.empty_like(merged)) if want_sides else (None, None)
+        flr, frl = (np.empty((h, w, 2), np.float32), np.empty((h, w, 2), np.float32)) if want_flows else (None, None)
+        rc = lib().s360_interpolate_views(self.h, alg.encode(), _p(il), _p(ir), w, h, _p(sh), n, _p(merged), _p(fl), _p(fr),
+                                          _p(flr), _p(frl))
+        if rc == _capi.ERR_UNKNOWN_ALG:
+            raise VrCamException(rc, "unrecognized flow algorithm name: " + alg)
+        self._ck(rc)
+        out = (merged,) + ((fl, fr) if want_sides else ()) + ((flr, frl) if want_flows else ())
+        return out if len(out) > 1 else merged
+
     def flatten_layers_deghost_prefer_base(self, bottom_layer, top_layer):
         b, t = _u8(bottom_layer), _u8(top_layer)
         out = np.empty_like(b)
