@@ -10,6 +10,8 @@
 // bilinear gather is two 16-byte loads; flow float2 (fx,fy).
 #include "flow_kernels.hpp"
 
+#include <cmath>
+#include <cstdlib>
 #include <stdexcept>
 
 #include "devmath.hpp"
@@ -101,6 +103,108 @@ __global__ __launch_bounds__(256) void k_resize_cubic_u8c4(const uchar4* __restr
   dst[(size_t)dy * dw + dx] = o;
 }
 
+// The same resize where the height does not change (sh == dh: the final resize of the 8k and 6k presets, 8400x4096 ->
+// 8192x4096 per eye). The vertical scale is exactly 1, so every row's source row is dy, its fraction 0 and its taps
+// (0, 2048, 0, 0): three of the four source rows k_resize_cubic_u8c4 reads and filters are multiplied by zero. Here only row
+// dy is read, and the vertical step is folded. With h1 the horizontal sum of that row (|h1| < 2^20):
+//  * SSE2-covered columns: float(h0) * 0 + float(h1) * 2^-11 + float(h2) * 0 + float(h3) * 0, added left to right. The
+//    three products are +-0, the tap 2048 * 2^-22 = 2^-11 is a power of two and float(h1) is exact, so the sum is
+//    float(h1) * 2^-11 bit for bit, except that a sum of zeros may be -0 instead of +0 — which rounds to the same integer 0;
+//  * the odd tail column: (h1 * 2048 + 2^21) >> 22.
+// A 256-wide, 16-high tile per workgroup: its source box (16 rows of at most HR_BW pixels — horizontal scales up to about
+// 1.2, checked by the launcher) goes to LDS in 16-byte pieces, a thread computes the double-precision coordinates and the
+// taps of its 4 adjacent columns once and produces those 4 pixels (one 16-byte store) of 4 rows: 4 LDS reads and 8 v_dot2
+// per pixel instead of 16 scattered global loads and 32.
+constexpr int HR_TW = 256, HR_TH = 16, HR_BW = 320;
+typedef unsigned u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));  // (rows start at any 4-byte address)
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__global__ __launch_bounds__(256) void k_resize_cubic_u8c4_h(const uchar4* __restrict__ src, int sw, int h, size_t sbs,
+                                                             uchar4* __restrict__ dst, int dw, size_t dbs, double scx) {
+  __shared__ __attribute__((aligned(16))) unsigned s_box[HR_TH][HR_BW];
+  const int tid = threadIdx.x, cx = tid & 63, q = tid >> 6;
+  const int tx0 = blockIdx.x * HR_TW, ty0 = blockIdx.y * HR_TH;
+  const unsigned* S = reinterpret_cast<const unsigned*>(src + sbs * blockIdx.z);
+  unsigned* D = reinterpret_cast<unsigned*>(dst + dbs * blockIdx.z);
+  // the box: columns bx0 (16-byte piece of the first column's first tap) .. the last column's last tap
+  int s0, s1;
+  float f;
+  resize_coord(min(tx0, dw - 1), scx, &s0, &f);
+  resize_coord(min(tx0 + HR_TW - 1, dw - 1), scx, &s1, &f);
+  const int bx0 = clip_idx(s0 - 1, sw) & ~3, bx1 = clip_idx(s1 + 2, sw);
+  const int np4 = (bx1 - bx0 + 4) >> 2, npieces = HR_TH * np4;  // np4 <= HR_BW / 4 (launcher)
+  constexpr int kIters = (HR_TH * (HR_BW / 4) + 255) / 256;
+  u32x4a4 ld[kIters];
+  // all pieces requested before the first is stored (index clamped, no early-out: see k_sepblur)
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int i = min(tid + it * 256, npieces - 1);
+    const int row = i / np4, gx = bx0 + 4 * (i - row * np4);
+    const unsigned* Sr = S + (size_t)min(ty0 + row, h - 1) * sw;
+    if (gx + 3 < sw) ld[it] = *reinterpret_cast<const u32x4a4*>(Sr + gx);
+    else ld[it] = u32x4a4{Sr[min(gx, sw - 1)], Sr[min(gx + 1, sw - 1)], Sr[min(gx + 2, sw - 1)], Sr[sw - 1]};  // never tapped behind sw - 1
+  }
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int i = tid + it * 256;
+    if (i >= npieces) continue;
+    const int row = i / np4, c4 = i - row * np4;
+    *reinterpret_cast<u32x4*>(&s_box[row][4 * c4]) = u32x4{ld[it].x, ld[it].y, ld[it].z, ld[it].w};  // (16-byte aligned: one ds_write_b128)
+  }
+  // this thread's 4 columns: tap positions in the box and the packed 11-bit taps
+  typedef short s16x2 __attribute__((ext_vector_type(2)));
+  const int dx0 = tx0 + 4 * cx;
+  int c[4][4];
+  s16x2 w01[4], w23[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int sx;
+    float cb[4];
+    resize_coord(min(dx0 + j, dw - 1), scx, &sx, &f);
+    cubic_coeffs(f, cb);
+    int a[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      a[k] = sat_s16(cv_round(cb[k] * 2048.f));
+      c[j][k] = clip_idx(sx - 1 + k, sw) - bx0;
+    }
+    w01[j] = __builtin_bit_cast(s16x2, (unsigned)(a[0] & 0xffff) | ((unsigned)a[1] << 16));
+    w23[j] = __builtin_bit_cast(s16x2, (unsigned)(a[2] & 0xffff) | ((unsigned)a[3] << 16));
+  }
+  __syncthreads();
+  if (dx0 >= dw) return;
+#pragma unroll
+  for (int r = 0; r < HR_TH / 4; ++r) {
+    const int row = q * (HR_TH / 4) + r, dy = ty0 + row;
+    if (dy >= h) break;
+    unsigned o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned p0 = s_box[row][c[j][0]], p1 = s_box[row][c[j][1]], p2 = s_box[row][c[j][2]], p3 = s_box[row][c[j][3]];
+      const bool sse = dx0 + j < (dw & ~1);
+      o[j] = 0;
+#pragma unroll
+      for (int ch = 0; ch < 4; ++ch) {
+        const unsigned sel = 0x0c040c00u + ch * 0x00010001u;
+        const s16x2 lo = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(p1, p0, sel));
+        const s16x2 hi = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(p3, p2, sel));
+        int h1 = __builtin_amdgcn_sdot2(lo, w01[j], 0, false);
+        h1 = __builtin_amdgcn_sdot2(hi, w23[j], h1, false);
+        // (|h1| < 2^20: cv_round's range check cannot fire, and h1 * 2048 fits)
+        const int v = sse ? (int)__builtin_rintf((float)h1 * (1.f / 2048)) : (h1 * 2048 + (1 << 21)) >> 22;
+        o[j] |= (unsigned)sat_u8(v) << (8 * ch);
+      }
+    }
+    unsigned* Dr = D + (size_t)dy * dw + dx0;
+    if (dx0 + 3 < dw) {
+      *reinterpret_cast<u32x4a4*>(Dr) = u32x4a4{o[0], o[1], o[2], o[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (dx0 + j < dw) Dr[j] = o[j];
+    }
+  }
+}
+
 // BGRA -> grey float in [0,1] (pre-blur) and alpha float (PixFlow.h:121-135).
 // cvtColor BGRA2GRAY 8-bit: (B*1868 + G*9617 + R*4899 + 2^13) >> 14; "/= 255.0f" == * float(1/255.).
 __global__ __launch_bounds__(256) void k_gray_alpha(const uchar4* __restrict__ src, size_t n, size_t sbs,
@@ -154,6 +258,24 @@ __global__ __launch_bounds__(256) void k_motion(const uchar4* __restrict__ cur, 
 //        operations in the same order (Gp = the previous flow's level, recv = the motion level, up.post_scale = the level's factor).
 // Tile: 64x16 outputs for the 3- and 5-tap kernels, 32x32 for the 15-tap ones (29 KB of LDS instead of 35 KB and 1.44x
 // instead of 1.9x row-pass halo work: blur15 + diffusion 100 -> 69 ms of summed kernel time per frame with 16 frames in flight).
+//
+// Known-result exit (EPI 2 / 3, `known_result` != 0; S360_KNOWN_RESULT=0 turns it off, results do not depend on it). The
+// alphas depend on the rig, not on the pictures, and on large parts of every level no pixel is updated. A workgroup votes once,
+// at the barrier behind the tile's LDS store (loads exactly as without the exit, all requested before the first is stored):
+// if no pixel of the tile has a0 > 0.9f && a1 > 0.9f, every record of the tile carries the NaN mark, and no RESULT of either
+// sweep kernel depends on anything else of such a record: sweep_quad.hip copies the fields and uses them only under `take`;
+// sweep_lock.hip evaluates only under `take` too, but its bulk service wave forms a (clamped) pre-touch address from
+// rec.z / rec.w of every pixel, updated or not, so the blurred-flow fields of a skipped tile must be finite and the same on
+// every run: they are written as 0 (EPI 3 keeps I0's gradient in the record as always). The tile skips the row pass, the column
+// pass and the barrier between them. rowflags stay untouched for it, as they always did. No condition on the flow values.
+// A tile with an updated pixel runs the code below unchanged.
+// Measured and NOT adopted: the same exit for the diffusion (EPI 1 / 4) on tiles where 1 - a0 * a1 == 0.0f everywhere, no centre
+// element is -0.0f and every loaded |v| < 2^100 (then cc * blur + (1 - cc) * flow is flow bit for bit). Exact (emulated and GPU
+// suites), and slower: 1.31 against 1.15 ms per frame — see DESIGN section 9.
+#ifdef S360_WAVE_EMULATION  // (CPU emulation only, like S360_QSTAT in sweep_quad.hip: tiles by the way they went)
+unsigned long long g_known_stats[2];  // tiles of the blur into records: exit taken, full
+#define S360_KSTAT(i) __atomic_fetch_add(&g_known_stats[i], 1ull, __ATOMIC_RELAXED)
+#endif
 struct UpSrc {  // SRC 2: geometry of the small source image and the scalar applied after the resize
   int sw, sh;
   size_t sbs;
@@ -166,7 +288,7 @@ __global__ __launch_bounds__(NT) void k_sepblur(const float* __restrict__ src, f
                                                  const float* __restrict__ A, FlowIdx idx,
                                                  const float2* __restrict__ Gp, void* __restrict__ recv,
                                                  float* const* __restrict__ dst_tab, UpSrc up,
-                                                 unsigned* __restrict__ rowflags) {
+                                                 unsigned* __restrict__ rowflags, int known_result) {
   constexpr int IW = SB_TW + 2 * R, IH = SB_TH + 2 * R;
   constexpr int IWP = IW | 1;  // odd row stride: the 4-wide row tasks of consecutive rows fall into different banks
   __shared__ __attribute__((aligned(8))) float s_in[IH][IWP][CN];
@@ -267,7 +389,38 @@ __global__ __launch_bounds__(NT) void k_sepblur(const float* __restrict__ src, f
     if (CN == 2) *reinterpret_cast<float2*>(&s_in[ly][lx][0]) = make_float2(ld[it][0], ld[it][CN - 1]);
     else s_in[ly][lx][0] = ld[it][0];
   }
-  __syncthreads();
+  if constexpr (EPI == 2 || EPI == 3) {  // known-result exit (header)
+    // the vote rides on the barrier that was here anyway: every wave leaves its verdict in a slot of its own
+    __shared__ int s_vote[NT / 64];
+    bool none = true;  // (alphas outside the image are 0 here)
+#pragma unroll
+    for (int o = 0; o < 4; ++o) none &= !(pa0[o] > 0.9f && pa1[o] > 0.9f);
+    s_vote[tid >> 6] = __ballot(!none) == 0ull;
+    __syncthreads();
+    int v = known_result != 0;
+#pragma unroll
+    for (int q = 0; q < NT / 64; ++q) v &= s_vote[q];
+    const bool known = __builtin_amdgcn_readfirstlane(v) != 0;  // workgroup-uniform
+#ifdef S360_WAVE_EMULATION
+    if (tid == 0) S360_KSTAT(known ? 0 : 1);
+#endif
+    if (known) {  // NaN-marked records with a finite, fixed flow behind the mark; a thread's pixels are those of its column task
+      if (tid < kColTasks) {
+        const int lx = tid % SB_TW, ly0 = (tid / SB_TW) * 4, gx = tx0 + lx;
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+          const int gy = ty0 + ly0 + o;
+          if (gx >= w || gy >= h) continue;
+          const size_t off = (size_t)gy * w + gx;
+          if (EPI == 2) static_cast<float2*>(recv)[bs * tile.z + off] = make_float2(__int_as_float(0x7fc00000), 0.0f);
+          else static_cast<float4*>(recv)[bs * tile.z + off] = make_float4(__int_as_float(0x7fc00000), pg[o].y, 0.0f, 0.0f);
+        }
+      }
+      return;
+    }
+  } else {
+    __syncthreads();
+  }
   // row pass: task = (row ly, group of 4 consecutive x). Two-channel images move through LDS as 8-byte pairs (one
   // ds_read_b64 per tap for both channels: half the LDS instructions and all banks in use).
   for (int t = tid; t < IH * (SB_TW / 4); t += NT) {
@@ -737,11 +890,28 @@ __global__ void k_search_init(const float* __restrict__ I, const float* __restri
   }
 }
 
+// S360_KNOWN_RESULT=0 turns the known-result short cuts off (k_sepblur's exit, the horizontal-only final resize): for A/B
+// runs and tests, the results do not depend on it. Read once per process.
+bool known_result_enabled() {
+  static const bool on = [] {
+    const char* e = std::getenv("S360_KNOWN_RESULT");
+    return !(e && e[0] == '0' && e[1] == 0);
+  }();
+  return on;
+}
+
 static inline dim3 grid2d(int w, int h, int B, dim3 blk) { return dim3((w + blk.x - 1) / blk.x, (h + blk.y - 1) / blk.y, B); }
 
 void launch_resize_cubic_u8c4(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* dst, int dw,
                               int dh, size_t dbs, int B, const uchar4* const* src_tab) {
   const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
+  // same height: one source row per output row (k_resize_cubic_u8c4_h), where a 256-column tile's source box fits (its
+  // taps span at most ceil(255 * scx) + 1 + 3 columns, the box starts up to 3 columns early and ends on a whole piece)
+  if (sh == dh && !src_tab && known_result_enabled() && (int)std::ceil((HR_TW - 1) * scx) + 12 <= HR_BW) {
+    hipLaunchKernelGGL(k_resize_cubic_u8c4_h, dim3((dw + HR_TW - 1) / HR_TW, (dh + HR_TH - 1) / HR_TH, B), dim3(256), 0, st,
+                       src, sw, sh, sbs, dst, dw, dbs, scx);
+    return;
+  }
   dim3 blk(32, 8);
   hipLaunchKernelGGL(k_resize_cubic_u8c4, grid2d(dw, dh, B, blk), blk, 0, st, src, sw, sh, sbs, dst, dw, dh, dbs, scx,
                      scy, src_tab);
@@ -764,10 +934,10 @@ static void launch_sepblur_t(hipStream_t st, const float* src, float* dst, int w
   if constexpr (R == 7) {  // 15x15: 32x32 tile — 29 KB of LDS, 1.44x row-pass halo work (64x16: 35 KB, 1.9x; measured 30 % slower);
     // 384 threads: the row pass has 46 rows x 8 groups = 368 tasks (two rounds on 256 threads, the second 44 % full)
     dim3 grd((w + 31) / 32, (h + 31) / 32, B);
-    hipLaunchKernelGGL((k_sepblur<R, CN, EPI, SRC, 32, 32, 384>), grd, dim3(64, 6), 0, st, src, dst, w, h, bs, t, A, idx, Gp, rec, dst_tab, up, rowflags);
+    hipLaunchKernelGGL((k_sepblur<R, CN, EPI, SRC, 32, 32, 384>), grd, dim3(64, 6), 0, st, src, dst, w, h, bs, t, A, idx, Gp, rec, dst_tab, up, rowflags, known_result_enabled() ? 1 : 0);
   } else {
     dim3 grd((w + 63) / 64, (h + 15) / 16, B);
-    hipLaunchKernelGGL((k_sepblur<R, CN, EPI, SRC>), grd, blk, 0, st, src, dst, w, h, bs, t, A, idx, Gp, rec, dst_tab, up, rowflags);
+    hipLaunchKernelGGL((k_sepblur<R, CN, EPI, SRC>), grd, blk, 0, st, src, dst, w, h, bs, t, A, idx, Gp, rec, dst_tab, up, rowflags, known_result_enabled() ? 1 : 0);
   }
 }
 void launch_sepblur(hipStream_t st, const float* src, float* dst, int w, int h, int cn, size_t bs, int B,

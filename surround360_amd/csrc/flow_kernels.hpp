@@ -25,6 +25,14 @@ struct PixFlowConsts {  // OpticalFlowFactory.h:26-41 / :45-60
   int maxPercentage;
 };
 
+// false when S360_KNOWN_RESULT=0 is set: the short cuts for work whose result is known before it is computed (the record
+// blur's tile exit, the horizontal-only final resize) are then off. Results do not depend on it; read once per process.
+bool known_result_enabled();
+#ifdef S360_WAVE_EMULATION
+// CPU emulation only: tiles of the 15x15 blur into the sweeps' records by the way they went — exit taken, full
+extern unsigned long long g_known_stats[2];
+#endif
+
 // src_tab (optional): device array of B source pointers used instead of src + sbs * b (images of a batch that do not
 // live in one allocation); likewise dst_tab / src_tab of the other launchers that take one.
 void launch_resize_cubic_u8c4(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* dst, int dw,

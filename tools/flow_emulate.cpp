@@ -59,3 +59,52 @@ extern "C" int emu_resize_linear_planes(const float* src, int sw, int sh, int B,
     return -1;
   }
 }
+
+// The INTER_CUBIC resize of BGRA images (B images sw x sh -> dw x dh): with sh == dh the horizontal-only kernel.
+extern "C" int emu_resize_cubic_u8c4(const uint8_t* src, int sw, int sh, int B, int dw, int dh, uint8_t* dst) {
+  try {
+    launch_resize_cubic_u8c4(nullptr, (const uchar4*)src, sw, sh, (size_t)sw * sh, (uchar4*)dst, dw, dh, (size_t)dw * dh, B);
+    return 0;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+
+// The 15x15 blur launchers with an epilogue on the alphas (flow_kernels.hip: k_sepblur EPI 1 - 4) on caller-made planes, one level of B flows:
+// flow / out B x h x w x 2, alpha n_images x h x w, flow b uses the alphas i0[b] and i1[b]. prev (B x h x w x 2) and motion
+// (n_images x h x w) given: launch_diffusion_adjust with prev_scale.
+extern "C" int emu_diffusion(const float* flow, const float* alpha, int w, int h, int B, const int* i0, const int* i1,
+                             const float* prev, const float* motion, float prev_scale, float* out) {
+  try {
+    const BlurTaps t = gaussian_taps(15, 8.0f);
+    const FlowIdx idx = {i0, i1};
+    const size_t n = (size_t)w * h;
+    if (prev) launch_diffusion_adjust(nullptr, (const float2*)flow, (float2*)out, w, h, n, B, t, alpha, idx, (const float2*)prev, motion, prev_scale);
+    else launch_diffusion(nullptr, (const float2*)flow, (float2*)out, w, h, n, B, t, alpha, idx);
+    return 0;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+// grad == nullptr: half-records (rec B x h x w x 2); grad (n_images x h x w x 2) given: full records (B x h x w x 4).
+// rowflags: B x h, as the caller initialised them.
+extern "C" int emu_blur_to_records(const float* flow, const float* alpha, const float* grad, int w, int h, int B, const int* i0,
+                                   const int* i1, float* rec, unsigned* rowflags) {
+  try {
+    const FlowIdx idx = {i0, i1};
+    launch_blur_to_records(nullptr, (const float2*)flow, rec, w, h, (size_t)w * h, B, gaussian_taps(15, 8.0f), (const float2*)grad, alpha,
+                           idx, rowflags);
+    return 0;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+// tiles of the blur into records by the way they went since the last reset: exit taken, full. Returns 0 when
+// S360_KNOWN_RESULT=0 is set.
+extern "C" int emu_known_result_stats(unsigned long long* out2, int reset) {
+  for (int i = 0; i < 2; ++i) {
+    if (out2) out2[i] = __atomic_load_n(&g_known_stats[i], __ATOMIC_RELAXED);
+    if (reset) __atomic_store_n(&g_known_stats[i], 0ull, __ATOMIC_RELAXED);
+  }
+  return known_result_enabled() ? 1 : 0;
+}
