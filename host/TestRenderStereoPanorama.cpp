@@ -63,7 +63,8 @@ struct Flags {
          // --num_gpus G: the 14 side pairs of the frame sharded over G GPUs, one RCCL strip gather
          {"num_gpus", "1"},
          // --num_frames N: frames frame_number .. +N-1 as ONE stream in this process (temporal state stays on the
-         // device, decode/upload/render/download/encode overlapped); output_equirect_path must contain %s or {frame}
+         // device, decode/upload/render/download/encode overlapped); output_equirect_path must contain %s or {frame}, and so
+         // must output_cubemap_path, which then names the cubemap of EVERY frame (rendered with the frame)
          // (the state files are written after the LAST frame only: that is what a later run resumes from)
          {"num_frames", "1"},
          // --num_streams S: the --num_frames frames as S independent streams, stream s = the s-th contiguous segment of the
@@ -743,7 +744,14 @@ static int run_job(const Flags& flags) {
   const s360_geometry& g = J.g;
   const std::string prev = F.s("prev_frame_data_dir");
   const bool cube = F.i("cubemap_width") > 0 && F.i("cubemap_height") > 0 && !F.s("output_cubemap_path").empty();
-  if (numFrames > 1 && cube) die("--output_cubemap_path is not available with --num_frames > 1");
+  // a stream leaves the cubemap of EVERY frame (the reference's caller asks for one beside every equirect,
+  // batch_process_video.py:40-47): rendered with the frame, fetched and written beside its equirect
+  const bool cubeStream = cube && numFrames > 1;
+  int cubeWhc[3] = {0, 0, 0};
+  if (cubeStream) {
+    ck(s360_set_cubemap_output(J.ctx[0], F.i("cubemap_width"), F.i("cubemap_height"), F.s("cubemap_format").c_str()), J.ctx[0]);
+    ck(s360_frame_cubemap_size(J.ctx[0], cubeWhc), J.ctx[0]);
+  }
 
   // ---- frame 0: decode, upload, previous-frame state from files, render
   const double ctxTime = now_sec();
@@ -766,6 +774,9 @@ static int run_job(const Flags& flags) {
   pngio::Pixels outBuf[kMaxEncoders + 1];
   std::thread encoder[kMaxEncoders + 1];  // encoder[i] owns outBuf[i] while it runs
   for (int i = 0; i <= kEncoders; ++i) outBuf[i].resize(numFrames > 1 || i == 0 ? outBytes : 0);
+  const size_t cubeBytes = !cubeStream ? 0 : devPng ? s360_frame_cubemap_png_bound(J.ctx[0]) : (size_t)cubeWhc[0] * cubeWhc[1] * 3;
+  pngio::Pixels cubeBuf[kMaxEncoders + 1];  // the frame's cubemap travels with its equirect: same fetch, same writer thread
+  for (int i = 0; i <= kEncoders && cubeStream; ++i) cubeBuf[i].resize(cubeBytes);
   int cur = 0;  // the buffer the next download goes to
   double renderEnd = renderStart, stateEnd = renderStart;
   double tDecode = 0, tUpload = 0, tFetch = 0, tJoin = 0;  // where the host thread of a stream spends its time (--v 1)
@@ -826,6 +837,11 @@ static int run_job(const Flags& flags) {
     if (devPng) ck(s360_frame_download_png(J.ctx[0], last ? 0 : 1, outBuf[cur].data(), outBuf[cur].size(), &pngBytes), J.ctx[0]);
     else if (last) ck(s360_frame_download_equirect(J.ctx[0], outBuf[cur].data()), J.ctx[0]);
     else ck(s360_frame_download_equirect_of(J.ctx[0], 1, outBuf[cur].data()), J.ctx[0]);  // frame k, while k+1 renders
+    size_t cubePngBytes = 0;
+    if (cubeStream) {
+      if (devPng) ck(s360_frame_download_cubemap_png(J.ctx[0], last ? 0 : 1, cubeBuf[cur].data(), cubeBuf[cur].size(), &cubePngBytes), J.ctx[0]);
+      else ck(s360_frame_download_cubemap(J.ctx[0], last ? 0 : 1, cubeBuf[cur].data()), J.ctx[0]);
+    }
     if (!leaving.empty()) {  // frame k is complete, so frame k+1's uploads (enqueued before it rendered) are long done
       ck(s360_frame_uploads_complete(J.ctx[0]), J.ctx[0]);
       for (auto& fi : leaving) spare.push_back(std::move(fi));
@@ -837,18 +853,29 @@ static int run_job(const Flags& flags) {
     // segment of one frame is named like the others)
     const std::string outPath = frame_path(F.s("output_equirect_path"), frame);
     const uint8_t* px = outBuf[cur].data();
-    if (devPng) encoder[cur] = std::thread([px, outPath, pngBytes] { save_bytes(outPath, px, pngBytes); });
-    else encoder[cur] = std::thread([px, outPath, &g] { save_png(outPath, px, g.out_width, g.out_height, 3); });  // TRSP:961
+    const std::string cubePath = cubeStream ? frame_path(F.s("output_cubemap_path"), frame) : std::string();
+    const uint8_t* cpx = cubeStream ? cubeBuf[cur].data() : nullptr;
+    const int cw = cubeWhc[0], chh = cubeWhc[1];
+    if (devPng)
+      encoder[cur] = std::thread([px, outPath, pngBytes, cpx, cubePath, cubePngBytes] {
+        save_bytes(outPath, px, pngBytes);
+        if (cpx) save_bytes(cubePath, cpx, cubePngBytes);
+      });
+    else
+      encoder[cur] = std::thread([px, outPath, &g, cpx, cubePath, cw, chh] {
+        save_png(outPath, px, g.out_width, g.out_height, 3);  // TRSP:961
+        if (cpx) save_png(cubePath, cpx, cw, chh, 3);          // TRSP:935
+      });
     // the reference writes the state of every frame; a stream only needs it to resume after its last frame. (Beside the
     // equirect's encoder, not in front of it.)
     if (F.b("write_state") && last) write_state(J, frame);
     stateEnd = now_sec();
-    if (last && cube) {  // optional stereo cubemap (TRSP:917-935)
+    if (last && cube && !cubeStream) {  // optional stereo cubemap (TRSP:917-935)
       int whc[3];
       ck(s360_frame_cubemap(J.ctx[0], F.i("cubemap_width"), F.i("cubemap_height"), F.s("cubemap_format").c_str(), whc, nullptr), J.ctx[0]);
       std::vector<uint8_t> cubeImg((size_t)whc[0] * whc[1] * 3);
       ck(s360_frame_cubemap(J.ctx[0], F.i("cubemap_width"), F.i("cubemap_height"), F.s("cubemap_format").c_str(), whc, cubeImg.data()), J.ctx[0]);
-      save_png(F.s("output_cubemap_path"), cubeImg.data(), whc[0], whc[1], 3);
+      save_png(frame_path(F.s("output_cubemap_path"), frame), cubeImg.data(), whc[0], whc[1], 3);  // (a stream segment of one frame is named like the others)
     }
     cur = numFrames > 1 ? (cur + 1) % (kEncoders + 1) : 0;
     const double tj = now_sec();
@@ -903,8 +930,7 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
   init_job(J, flags);
   Flags& F = J.F;
   const int verbose = F.i("v");
-  if (F.i("cubemap_width") > 0 && F.i("cubemap_height") > 0 && !F.s("output_cubemap_path").empty())
-    die("--output_cubemap_path is not available with --num_streams");
+  const bool cube = F.i("cubemap_width") > 0 && F.i("cubemap_height") > 0 && !F.s("output_cubemap_path").empty();
   const int S = (int)segs.size();
   J.ctx.assign(1, nullptr);
   if (s360_create(&J.ctx[0], device, J.cams.data(), J.ncams, &J.prm) < 0) die(s360_last_error(nullptr));
@@ -925,6 +951,16 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
   if (devPng) ck(s360_set_png_encode(ctx, 1), ctx);
   const size_t outBytes = devPng ? s360_frame_png_bound(ctx) : (size_t)g.out_width * g.out_height * 3;
   std::vector<size_t> pngBytes(S, 0);
+  // the cubemap of every frame of every stream (batch_process_video.py:40-47), rendered for all slots of a step in one launch
+  int cubeWhc[3] = {0, 0, 0};
+  if (cube) {
+    ck(s360_set_cubemap_output(ctx, F.i("cubemap_width"), F.i("cubemap_height"), F.s("cubemap_format").c_str()), ctx);
+    ck(s360_frame_cubemap_size(ctx, cubeWhc), ctx);
+  }
+  const size_t cubeBytes = !cube ? 0 : devPng ? s360_frame_cubemap_png_bound(ctx) : (size_t)cubeWhc[0] * cubeWhc[1] * 3;
+  std::vector<size_t> cubePngBytes(S, 0);
+  std::vector<pngio::Pixels> cubeBuf(cube ? S : 0);
+  for (auto& b : cubeBuf) b.resize(cubeBytes);
 
   int steps = 0;
   for (const Segment& sg : segs) steps = std::max(steps, sg.n);
@@ -998,6 +1034,10 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
           // (the first fetch of a step waits for the step)
           if (devPng) ck(s360_frame_download_png_slot(ctx, s, age, outBuf[s].data(), outBuf[s].size(), &pngBytes[s]), ctx);
           else ck(s360_frame_download_equirect_slot(ctx, s, age, outBuf[s].data()), ctx);
+          if (cube) {
+            if (devPng) ck(s360_frame_download_cubemap_png_slot(ctx, s, age, cubeBuf[s].data(), cubeBuf[s].size(), &cubePngBytes[s]), ctx);
+            else ck(s360_frame_download_cubemap_slot(ctx, s, age, cubeBuf[s].data()), ctx);
+          }
           if (F.b("write_state") && k + 1 == segs[s].n) {
             std::lock_guard<std::mutex> sel(selMu);
             ck(s360_select_frame_slot(ctx, s), ctx);
@@ -1016,8 +1056,20 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
           const std::string outPath = frame_path(F.s("output_equirect_path"), name[s]);
           const uint8_t* px = outBuf[s].data();
           const size_t nb = pngBytes[s];
-          if (devPng) encoder[s] = std::thread([px, outPath, nb] { save_bytes(outPath, px, nb); });
-          else encoder[s] = std::thread([px, outPath, &g] { save_png(outPath, px, g.out_width, g.out_height, 3); });
+          const std::string cubePath = cube ? frame_path(F.s("output_cubemap_path"), name[s]) : std::string();
+          const uint8_t* cpx = cube ? cubeBuf[s].data() : nullptr;
+          const size_t cnb = cubePngBytes[s];
+          const int cw = cubeWhc[0], chh = cubeWhc[1];
+          if (devPng)
+            encoder[s] = std::thread([px, outPath, nb, cpx, cubePath, cnb] {
+              save_bytes(outPath, px, nb);
+              if (cpx) save_bytes(cubePath, cpx, cnb);
+            });
+          else
+            encoder[s] = std::thread([px, outPath, &g, cpx, cubePath, cw, chh] {
+              save_png(outPath, px, g.out_width, g.out_height, 3);
+              if (cpx) save_png(cubePath, cpx, cw, chh, 3);
+            });
           name[s] = next_frame_name(name[s]);
         }
     }
@@ -1082,6 +1134,10 @@ int main(int argc, char** argv) {
   Flags F;
   F.parse(argc, argv);
   const int streams = std::max(1, F.i("num_streams")), frames = std::max(1, F.i("num_frames"));
+  if (frames > 1 && F.i("cubemap_width") > 0 && F.i("cubemap_height") > 0 && !F.s("output_cubemap_path").empty() &&
+      frame_path(F.s("output_cubemap_path"), "0") == frame_path(F.s("output_cubemap_path"), "1"))
+    die("--output_cubemap_path must contain %s or {frame} with --num_frames > 1: " + std::to_string(frames) +
+        " frames would be written to one file, " + F.s("output_cubemap_path"));
   if (frames > 1) {
     const char* e = std::getenv("S360_PNG_THREADS");  // (developer switch)
     // three encoders and 51 decoder threads share the CPUs the process may use: half of them per encoder

@@ -280,6 +280,7 @@ int s360_frame_uploads_complete(s360_ctx* ctx);
  * SR/render/ImageWarper.cpp:95-141, SR/util/CvUtil.cpp:117-138, TRSP:917-935): format "video" (3 x 2 faces per eye,
  * flipped) or "photo" (6 faces stacked). whc receives width/height/3; out_bgr may be NULL for a size query. */
 int s360_frame_cubemap(s360_ctx* ctx, int face_width, int face_height, const char* format, int whc[3], uint8_t* out_bgr);
+/* The cubemap as an output of EVERY frame of a stream or batch: s360_cubemap.h (included at the end of this header). */
 /* Intermediates for stage-by-stage parity tests and for the reference's on-disk state
  * (overlap_<i>_{L,R}.png, flow{LtoR,RtoL}_<i>.bin, extended*Spherical_<eye>.png, flow_<eye>.bin).
  * Names: "projection"(idx cam) "overlap_l" "overlap_r" "side_pano_l" "side_pano_r" "top_spherical"
@@ -529,4 +530,5 @@ int s360_isp_config_tables(const s360_isp_config* cfg, float* ccm9, float* lut, 
 #ifdef __cplusplus
 }
 #endif
+#include "s360_cubemap.h" /* per-frame cubemap output of the stream / batch hosts */
 #endif /* S360_H_ */

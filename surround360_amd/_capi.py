@@ -85,6 +85,11 @@ SYMBOLS = [
     "s360_host_alloc", "s360_host_free", "s360_frame_uploads_complete",
     "s360_set_output_double_buffer", "s360_set_png_encode", "s360_frame_png_bound", "s360_frame_download_png", "s360_frame_download_png_slot", "s360_frame_download_equirect_slot", "s360_png_bound", "s360_encode_png",
 ]
+# ... and every symbol include/s360_cubemap.h declares (the cubemap of every frame; s360.h includes that header)
+CUBEMAP_SYMBOLS = [
+    "s360_set_cubemap_output", "s360_frame_cubemap_size", "s360_frame_download_cubemap", "s360_frame_download_cubemap_slot",
+    "s360_frame_cubemap_png_bound", "s360_frame_download_cubemap_png", "s360_frame_download_cubemap_png_slot",
+]
 
 _lib = None
 
@@ -110,6 +115,8 @@ def lib():
         L.s360_host_free.restype = None
         L.s360_frame_png_bound.restype = C.c_size_t
         L.s360_frame_png_bound.argtypes = [C.c_void_p]
+        L.s360_frame_cubemap_png_bound.restype = C.c_size_t
+        L.s360_frame_cubemap_png_bound.argtypes = [C.c_void_p]
         L.s360_png_bound.restype = C.c_size_t
         L.s360_png_bound.argtypes = [C.c_int, C.c_int]
         L.s360_host_free.argtypes = [C.c_void_p]

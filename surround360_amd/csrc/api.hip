@@ -1096,6 +1096,108 @@ int s360_frame_uploads_complete(s360_ctx* c) {
   });
 }
 
+/* ---- the stereo cubemap of every frame (TRSP:917-935 for a stream or a batch) ---- */
+int s360_set_cubemap_output(s360_ctx* c, int face_w, int face_h, const char* format) {
+  return frame_guard(c, [&] {
+    need(c, "null ctx");
+    if (face_w == 0 || face_h == 0) { c->cube_fw = c->cube_fh = 0; return; }
+    need(format, "bad argument");
+    const std::string f(format);
+    if (f != "video" && f != "photo")  // CvUtil.cpp:134-137
+      throw Error(S360_ERR_INVALID_ARG, "unexpected cubemap format: " + f + ". valid formats are: video,photo");
+    need(face_w > 0 && face_h > 0 && face_w <= 16384 && face_h <= 16384, "cubemap face size must be in 1..16384 (0 = off)");
+    (void)cube_maps(c, face_w, face_h, f == "video");  // maps + prepared form now (a host wait), not inside a frame
+    c->cube_fw = face_w; c->cube_fh = face_h; c->cube_video = f == "video";
+  });
+}
+int s360_frame_cubemap_size(s360_ctx* c, int whc[3]) {
+  return guard(c, [&] {
+    need(c && whc, "bad argument");
+    if (c->cube_fw <= 0 || c->cube_fh <= 0) throw Error(S360_ERR_STATE, "the cubemap output is off (s360_set_cubemap_output)");
+    whc[0] = c->cube_video ? 3 * c->cube_fw : c->cube_fw;
+    whc[1] = c->cube_video ? 4 * c->cube_fh : 12 * c->cube_fh;
+    whc[2] = 3;
+  });
+}
+// what the fetches of one output buffer share: the download stream and its events (download_equirect_impl)
+static void ensure_download_stream(s360_ctx* c) {
+  if (!c->stDown) S360_HIP(hipStreamCreateWithFlags(&c->stDown, hipStreamNonBlocking));
+  if (!c->evDown) S360_HIP(hipEventCreateWithFlags(&c->evDown, hipEventDisableTiming | hipEventBlockingSync));
+  if (!c->downErr) {
+    S360_HIP(hipHostMalloc((void**)&c->downErr, 4 * sizeof(unsigned), hipHostMallocDefault));
+    std::memset(c->downErr, 0, 4 * sizeof(unsigned));
+  }
+}
+static int cube_buffer(s360_ctx* c, FrameState& F, int age) {
+  need(F.frames_done > age, "that frame has not been rendered");
+  need(age == 0 || ((c->pipeline || c->two_outputs) && F.outBGR[F.out_cur ^ 1].p),
+       "age 1 needs two output buffers (s360_set_frame_pipelining or s360_set_output_double_buffer)");
+  const int b = age == 0 ? F.out_cur : F.out_cur ^ 1;
+  if (F.cubeFrame[b] != F.frames_done - 1 - age || !F.cubeBGR[b].p)
+    throw Error(S360_ERR_STATE, "that frame was rendered without s360_set_cubemap_output");
+  return b;
+}
+static int download_cubemap_impl(s360_ctx* c, int slot, int age, uint8_t* out_bgr) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard_l(c, [&](std::unique_lock<std::recursive_mutex>& lk) {
+    need(out_bgr && (age == 0 || age == 1), "bad argument (age is 0 = latest enqueued frame or 1 = the one before)");
+    FrameState& F = slot_state(c, slot);
+    const int b = cube_buffer(c, F, age);
+    // as download_equirect_impl: wait for THAT frame only, copy on the download stream, the context free meanwhile
+    ensure_download_stream(c);
+    if (!F.downRead[b]) S360_HIP(hipEventCreateWithFlags(&F.downRead[b], hipEventDisableTiming));
+    S360_HIP(hipStreamWaitEvent(c->stDown, F.outDone[b], 0));
+    S360_HIP(hipMemcpyAsync(out_bgr, F.cubeBGR[b].p, (size_t)F.cubeOutW[b] * F.cubeOutH[b] * 3, hipMemcpyDeviceToHost, c->stDown));
+    if (F.outErrDev[b].p) S360_HIP(hipMemcpyAsync(c->downErr, F.outErrDev[b].p, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stDown));
+    S360_HIP(hipEventRecord(F.downRead[b], c->stDown));
+    S360_HIP(hipEventRecord(c->evDown, c->stDown));
+    const hipEvent_t ev = c->evDown;
+    const unsigned* errw = F.outErrDev[b].p ? c->downErr : nullptr;
+    lk.unlock();
+    const hipError_t rc = hipEventSynchronize(ev);
+    lk.lock();
+    S360_HIP(rc);
+    if (errw && (errw[0] | errw[1] | errw[2])) {
+      for (FlowEngine* e : {c->flow.get(), c->flow_pole.get(), c->flow_pr.get()})
+        if (e) (void)e->take_error(c->st);
+      throw Error(S360_ERR_HIP, "banded sweep timed out waiting for a neighbour band (results invalid)");
+    }
+  });
+}
+int s360_frame_download_cubemap(s360_ctx* c, int age, uint8_t* out_bgr) { return download_cubemap_impl(c, -1, age, out_bgr); }
+int s360_frame_download_cubemap_slot(s360_ctx* c, int slot, int age, uint8_t* out_bgr) {
+  if (slot < 0) return S360_ERR_INVALID_ARG;
+  return download_cubemap_impl(c, slot, age, out_bgr);
+}
+size_t s360_frame_cubemap_png_bound(s360_ctx* c) {
+  size_t n = 0;
+  if (!c) return 0;
+  (void)guard(c, [&] {
+    if (c->cube_fw > 0 && c->cube_fh > 0)
+      n = PngPlan::make(c->cube_video ? 3 * c->cube_fw : c->cube_fw, c->cube_video ? 4 * c->cube_fh : 12 * c->cube_fh).file_bound;
+  });
+  return n;
+}
+static int download_cubemap_png_impl(s360_ctx* c, int slot, int age, uint8_t* out, size_t cap, size_t* n_out) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard_l(c, [&](std::unique_lock<std::recursive_mutex>& lk) {
+    need(out && n_out && (age == 0 || age == 1), "bad argument (age is 0 = latest enqueued frame or 1 = the one before)");
+    FrameState& F = slot_state(c, slot);
+    const int b = cube_buffer(c, F, age);
+    if (F.cubePngFrame[b] != F.frames_done - 1 - age || !F.cubePngFile[b].p)
+      throw Error(S360_ERR_STATE, "that frame was rendered without s360_set_png_encode");
+    if (!F.downRead[b]) S360_HIP(hipEventCreateWithFlags(&F.downRead[b], hipEventDisableTiming));
+    png_fetch(c, lk, F.cubePngPlan[b], F.cubePngMeta[b], F.cubePngFile[b], F.outDone[b], F.downRead[b], F.outErrDev[b].p, out, cap, n_out);
+  });
+}
+int s360_frame_download_cubemap_png(s360_ctx* c, int age, uint8_t* out, size_t cap, size_t* n_out) {
+  return download_cubemap_png_impl(c, -1, age, out, cap, n_out);
+}
+int s360_frame_download_cubemap_png_slot(s360_ctx* c, int slot, int age, uint8_t* out, size_t cap, size_t* n_out) {
+  if (slot < 0) return S360_ERR_INVALID_ARG;
+  return download_cubemap_png_impl(c, slot, age, out, cap, n_out);
+}
+
 int s360_frame_cubemap(s360_ctx* c, int face_w, int face_h, const char* format, int whc[3], uint8_t* out_bgr) {
   return frame_guard(c, [&] {
     need(c && format && whc, "bad argument");

@@ -89,6 +89,14 @@ struct s360_ctx {
   struct PackedMap { s360::DevBuf packed, tiles; int sw = -1, sh = -1; hipEvent_t ready = nullptr; };
   struct PackedCache { std::vector<std::unique_ptr<PackedMap>> e; };
   PackedCache sidePk, topPk, botPk;
+  // s360_set_cubemap_output: every finished frame also leaves its stereo cubemap (0 x 0 = off). The face warp maps depend
+  // only on the sizes: one entry per (face size, eye size) for all slots — the float maps [6][fh][fw] as the host computes them
+  // (also what s360_frame_cubemap reads) and, per format (0 photo, 1 video), their prepared form for k_cubemap_tiles. Entries are
+  // built with a host wait and never rebuilt or freed before the context is: a frame in flight may still read the one it was
+  // enqueued with.
+  int cube_fw = 0, cube_fh = 0, cube_video = 1;
+  struct CubeMaps { int fw = 0, fh = 0, W = 0, H = 0, lds_pixels = 0; s360::DevBuf maps, packed[2], tiles[2]; };
+  std::vector<std::unique_ptr<CubeMaps>> cubeMaps;
   bool maps_ready = false;
   hipEvent_t evMaps = nullptr;  // behind the kernels that built the float maps (the pack kernels may run on another stream)
   void make_current() const { S360_HIP(hipSetDevice(device)); }

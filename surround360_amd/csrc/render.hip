@@ -937,6 +937,34 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
       launch_sharpen_many(st, imgs.data() + i, lps, scr, n, W, H, 1.0f + (float)c->P.sharpening);
     }
   }
+  // s360_set_cubemap_output: the stereo cubemap of every slot's frame from its sharpened eyes (TRSP:917-935 follows the
+  // sharpenThreads), both eyes of all slots in ONE launch through the context's prepared map; each slot's cubemap lands in the
+  // buffer with the index of the equirect's (the loop below records outDone behind both)
+  const bool cube = c->cube_fw > 0 && c->cube_fh > 0;
+  if (cube) {
+    const int fw = c->cube_fw, fh = c->cube_fh, video = c->cube_video;
+    const int cw = video ? 3 * fw : fw, ch = video ? 4 * fh : 12 * fh;
+    const s360_ctx::CubeMaps& M = cube_maps(c, fw, fh, video);
+    std::vector<const uchar4*> eyes;
+    std::vector<uint8_t*> outs;
+    const DevTables* tab = nullptr;
+    for (int k : slotIds) {
+      SlotScope ss(c, k);
+      FrameState& F = frame_state(c);
+      const int ob = (c->pipeline || c->two_outputs) ? F.out_cur ^ 1 : F.out_cur;
+      F.cubeBGR[ob].ensure((size_t)cw * ch * 3);
+      if (F.downRead[ob]) S360_HIP(hipStreamWaitEvent(st, F.downRead[ob], 0));  // a fetch of the frame this buffer held may still run
+      for (int e = 0; e < 2; ++e) eyes.push_back(F.pano[e].as<uchar4>());
+      outs.push_back(F.cubeBGR[ob].as<uint8_t>());
+      F.cubeOutW[ob] = cw;
+      F.cubeOutH[ob] = ch;
+      F.cubeFrame[ob] = F.frames_done;
+      tab = &F.tab.dev;
+    }
+    ProfScope ps(prof, "cubemap_stream");
+    launch_cubemap_tiles(st, eyes.data(), outs.data(), (int)outs.size(), W, H, M.maps.as<float2>(), M.packed[video].as<unsigned>(),
+                         M.tiles[video].p, fw, fh, video, M.lds_pixels, *tab);
+  }
   for (int k : slotIds) {
     SlotScope ss(c, k);
     FrameState& F = frame_state(c);
@@ -965,6 +993,14 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
         F.pngFile[ob].ensure(F.pngPlan[ob].file_bound);
         png_encode_enqueue(st, F.outBGR[ob].as<uint8_t>(), F.pngPlan[ob], F.sc->pngScratch, F.pngMeta[ob], F.pngFile[ob].as<uint8_t>());
         F.pngFrame[ob] = F.frames_done;
+      }
+      if (cube && c->png_encode) {  // the cubemap's file image: the same encoder behind the equirect's, through the same segments
+        ProfScope ps(prof, "png_encode");
+        F.cubePngPlan[ob] = PngPlan::make(F.cubeOutW[ob], F.cubeOutH[ob]);
+        F.cubePngFile[ob].ensure(F.cubePngPlan[ob].file_bound);
+        png_encode_enqueue(st, F.cubeBGR[ob].as<uint8_t>(), F.cubePngPlan[ob], F.sc->pngScratch, F.cubePngMeta[ob],
+                           F.cubePngFile[ob].as<uint8_t>());
+        F.cubePngFrame[ob] = F.frames_done;
       }
       if (!F.outErrDev[ob].p) {
         F.outErrDev[ob].ensure(4 * sizeof(unsigned));
@@ -1052,12 +1088,13 @@ void cube_map_entry(float x, float y, int face, int srcCols, int srcRows, float 
 }
 }  // namespace
 
-void frame_cubemap(s360_ctx* c, int fw, int fh, bool video, int* ow, int* oh) {
-  FrameState& F = frame_state(c);
+s360_ctx::CubeMaps& cube_maps(s360_ctx* c, int fw, int fh, int video) {
   if (fw <= 0 || fh <= 0) throw Error(S360_ERR_INVALID_ARG, "cubemap face size must be positive");
-  if (!F.pano[0].p || !F.pano[1].p || !F.frames_done) throw Error(S360_ERR_STATE, "no frame rendered yet");
   const int W = c->P.eqr_width, H = c->P.eqr_height;
-  if (F.cubeW != fw || F.cubeH != fh || F.cubeSrcW != W || F.cubeSrcH != H) {
+  s360_ctx::CubeMaps* M = nullptr;
+  for (auto& e : c->cubeMaps)
+    if (e->fw == fw && e->fh == fh && e->W == W && e->H == H) M = e.get();
+  if (!M) {
     static const int faces[6] = {CUBE_RIGHT, CUBE_LEFT, CUBE_TOP, CUBE_BOTTOM, CUBE_BACK, CUBE_FRONT};
     std::vector<float> m((size_t)6 * fw * fh * 2);
     const float dy = 1.0f / float(fw), dx = 1.0f / float(fh);
@@ -1067,16 +1104,41 @@ void frame_cubemap(s360_ctx* c, int fw, int fh, bool video, int* ow, int* oh) {
           float* e = &m[(((size_t)f * fh + j) * fw + i) * 2];
           cube_map_entry(float(i) * dy - 0.5f, float(j) * dx - 0.5f, faces[f], W, H, (float)M_PI, e, e + 1);
         }
-    F.cubeMaps.ensure(m.size() * sizeof(float));
-    S360_HIP(hipMemcpyAsync(F.cubeMaps.p, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice, c->st));
-    S360_HIP(hipStreamSynchronize(c->st));  // `m` is freed on return
-    F.cubeW = fw; F.cubeH = fh; F.cubeSrcW = W; F.cubeSrcH = H;
+    auto n = std::make_unique<s360_ctx::CubeMaps>();
+    n->maps.ensure(m.size() * sizeof(float));
+    S360_HIP(hipMemcpyAsync(n->maps.p, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice, c->st_user));
+    S360_HIP(hipStreamSynchronize(c->st_user));  // `m` is freed on return; every stream may read the maps from here on
+    n->fw = fw; n->fh = fh; n->W = W; n->H = H;
+    n->lds_pixels = cubemap_lds_pixels();
+    c->cubeMaps.push_back(std::move(n));
+    M = c->cubeMaps.back().get();
   }
+  if (video >= 0 && !M->packed[video].p) {
+    const size_t px = (size_t)6 * fw * fh;
+    DevBuf packed, tiles;
+    packed.ensure(px * sizeof(unsigned));
+    tiles.ensure(cubemap_tile_count(fw, fh) * 16);
+    launch_cubemap_pack(c->st_user, M->maps.as<float2>(), W, H, fw, fh, video, M->lds_pixels, packed.as<unsigned>(), tiles.p);
+    S360_HIP(hipStreamSynchronize(c->st_user));
+    std::swap(M->packed[video].p, packed.p);
+    std::swap(M->packed[video].cap, packed.cap);
+    std::swap(M->tiles[video].p, tiles.p);
+    std::swap(M->tiles[video].cap, tiles.cap);
+  }
+  return *M;
+}
+
+void frame_cubemap(s360_ctx* c, int fw, int fh, bool video, int* ow, int* oh) {
+  FrameState& F = frame_state(c);
+  if (fw <= 0 || fh <= 0) throw Error(S360_ERR_INVALID_ARG, "cubemap face size must be positive");
+  if (!F.pano[0].p || !F.pano[1].p || !F.frames_done) throw Error(S360_ERR_STATE, "no frame rendered yet");
+  const int W = c->P.eqr_width, H = c->P.eqr_height;
+  const s360_ctx::CubeMaps& M = cube_maps(c, fw, fh, -1);
   *ow = video ? 3 * fw : fw;
   *oh = video ? 4 * fh : 12 * fh;
   F.cubeOut.ensure((size_t)*ow * *oh * 3);
   ProfScope ps(c->prof, "cubemap");
-  launch_cubemap(c->st, F.pano[0].as<uchar4>(), F.pano[1].as<uchar4>(), W, H, F.cubeMaps.as<float2>(), fw, fh, video ? 1 : 0,
+  launch_cubemap(c->st, F.pano[0].as<uchar4>(), F.pano[1].as<uchar4>(), W, H, M.maps.as<float2>(), fw, fh, video ? 1 : 0,
                  F.cubeOut.as<uint8_t>(), F.tab.dev);
 }
 

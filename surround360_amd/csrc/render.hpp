@@ -103,8 +103,16 @@ struct FrameState {
   DevBuf botSrc2, prRed[2], prImgs[2], prFlow[2], prTmp, prWarp, prMerged;
   bool have_pr_inputs = false, have_prev_pr = false;
   int last_pr = 0;
-  DevBuf cubeMaps, cubeOut;  // cached face warp maps [6][fh][fw] float2 and the stacked BGR cubemap
-  int cubeW = 0, cubeH = 0, cubeSrcW = 0, cubeSrcH = 0;
+  DevBuf cubeOut;  // s360_frame_cubemap's stacked BGR cubemap (the face maps are the context's: ctx.hpp CubeMaps)
+  // s360_set_cubemap_output: the stacked cubemap of the frame in outBGR[i] (the finish stage renders it behind the sharpen and in
+  // front of outDone[i]; outDone / downRead cover both outputs), its size, the frame (frames_done) it belongs to, and with
+  // s360_set_png_encode its file image. Allocated only while the feature is on.
+  DevBuf cubeBGR[2];
+  int cubeOutW[2] = {0, 0}, cubeOutH[2] = {0, 0};
+  long long cubeFrame[2] = {-1, -1};
+  DevBuf cubePngFile[2], cubePngMeta[2];
+  PngPlan cubePngPlan[2];
+  long long cubePngFrame[2] = {-1, -1};
 };
 
 FrameState& frame_state(s360_ctx* c);
@@ -124,6 +132,9 @@ void frame_render_slots(s360_ctx* c, const int* slots, int n, int use_prev);  //
 void set_frame_slots(s360_ctx* c, int n);
 // stereo cubemap of the last finished frame into F.cubeOut; returns its width/height through ow/oh
 void frame_cubemap(s360_ctx* c, int face_w, int face_h, bool video, int* ow, int* oh);
+// the context's face maps for (face size, eye size), with their prepared form for `video` (0 / 1) when video >= 0: built on
+// first use (host arithmetic, upload, pack kernel, host wait), then shared by every slot and stream
+s360_ctx::CubeMaps& cube_maps(s360_ctx* c, int face_w, int face_h, int video);
 
 // RCCL strip gather of the sharded frame (comm.cpp)
 void comm_unique_id(void* id128);

@@ -1433,6 +1433,209 @@ __global__ __launch_bounds__(256) void k_cubemap(const uchar4* __restrict__ eyeL
   o[2] = (uint8_t)sat_u8((s2 + (1 << 14)) >> 15);
 }
 
+// ---- the cubemap of EVERY frame (s360_set_cubemap_output): prepared map + LDS tiles ---------------------------------
+// The same arithmetic as k_cubemap — remap INTER_CUBIC from the 1/32-pixel table, BORDER_WRAP in x and y, three channels,
+// (s + 2^14) >> 15 saturated — in the form of the packed remap above: everything that depends only on the sizes is prepared
+// ONCE per (face size, eye size, format) by k_cubemap_pack, in the stacked output's own pixel order (face order and the
+// "video" layout's horizontal flip baked in; the two eyes share one prepared half): per output pixel one dword {1 | tap
+// origin relative to the tile's source box (10 + 11 bits) | fraction index (10 bits)}, per tile of CT_W x CT_H output
+// pixels of ONE face (tiles never cross a face edge, whatever the face size) the box of eye pixels its taps touch.
+// k_cubemap_tiles then has one memory phase per tile (packed dwords + box, requested together), the box in LDS, 16 LDS
+// taps per pixel folded with v_perm_b32 + v_dot2_i32_i16, and four pixels per thread leaving as three dwords (scalar
+// byte stores when the face width is not a multiple of 4). One launch covers both eyes of every slot of a batch
+// (grid.z = 2 x slots through a table of pointers): the prepared map is read from L2 after the first slot.
+// BORDER_WRAP: box coordinates are UNWRAPPED — the origin may be -1 or reach past the last column / row — and the box
+// LOAD wraps (per box pixel, not per tap). A tile that straddles the theta = 0 / 2 pi seam has taps at both ends of the
+// eye's rows: its box is compact modulo the width, so the pack kernel also measures the box with the left half's columns
+// moved up by one width and keeps the narrower of the two; such a tile is an ordinary tile. What has no compact box — the
+// rings around the centres of TOP and BOTTOM, where every theta meets and taps wrap in y — takes the per-tap gather from
+// the float map. Tile shape: the top / bottom faces' iso-theta lines turn through every direction, so a square tile has the
+// smallest worst-case box; counted on the host (float64 restatement of the map, 8400 x 4096 eyes -> 1536^2 faces):
+// 16 x 16 tiles with a 4096-pixel box leave 2.2 % of the pixels to the gather (64 x 16: 24.6 %, 32 x 16: 7.7 %); a
+// 2560-pixel box (S360_CUBEMAP_LDS_PIXELS, more waves per CU) 4.9 %.
+constexpr int CT_W = 16, CT_H = 16;
+struct CubeJobs {  // per launch: BGRA eyes [2 * slot + eye] and stacked BGR outputs [slot]
+  const uchar4* eye[2 * kCubeMaxSlots];
+  uint8_t* out[kCubeMaxSlots];
+};
+struct CubeGeom { int fw, fh, video, ow, eyeH, txN, tyN; };
+// face slot s of the stacked layout (one eye): origin in the output, index in the maps' face list
+__device__ __forceinline__ void cube_face_slot(const CubeGeom& G, int s, int* fx0, int* fy0, int* list) {
+  if (G.video) {  // rows {LEFT, RIGHT, TOP}, {BOTTOM, BACK, FRONT} = list indices {1, 0, 2}, {3, 4, 5}
+    const int row = s >= 3, col = s - 3 * row;
+    *fx0 = col * G.fw; *fy0 = row * G.fh; *list = s < 2 ? 1 - s : s;
+  } else {
+    *fx0 = 0; *fy0 = s * G.fh; *list = s;
+  }
+}
+__device__ __forceinline__ size_t cube_map_index(const CubeGeom& G, int list, int lx, int ly) {
+  return ((size_t)list * G.fh + ly) * G.fw + (G.video ? G.fw - 1 - lx : lx);  // (video: faces flipped horizontally)
+}
+
+template <int CAP>
+__global__ __launch_bounds__(64) void k_cubemap_pack(const float2* __restrict__ maps /*[6][fh][fw]*/, int sw, int sh, CubeGeom G,
+                                                     unsigned* __restrict__ packed /*[eyeH][ow]*/, int4* __restrict__ tiles) {
+  int fx0, fy0, list;
+  cube_face_slot(G, blockIdx.z, &fx0, &fy0, &list);
+  const int lx0 = blockIdx.x * CT_W + (threadIdx.x & 3) * 4, ly = blockIdx.y * CT_H + (threadIdx.x >> 2);
+  const int half = sw >> 1;
+  int sx[4], sy[4], fxy[4];
+  int mnx = INT_MAX, mxx = INT_MIN, mns = INT_MAX, mxs = INT_MIN, mny = INT_MAX, mxy = INT_MIN;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    sx[k] = sy[k] = fxy[k] = 0;
+    if (lx0 + k < G.fw && ly < G.fh) {
+      const float2 m = maps[cube_map_index(G, list, lx0 + k, ly)];
+      remap_coord(m.x, m.y, &sx[k], &sy[k], &fxy[k]);
+      const int xs = sx[k] + (sx[k] < half ? sw : 0);  // the seam's view of this column
+      mnx = min(mnx, sx[k]); mxx = max(mxx, sx[k]);
+      mns = min(mns, xs); mxs = max(mxs, xs);
+      mny = min(mny, sy[k]); mxy = max(mxy, sy[k]);
+    }
+  }
+  mnx = wave_min_i(mnx); mxx = wave_max_i(mxx);
+  mns = wave_min_i(mns); mxs = wave_max_i(mxs);
+  mny = wave_min_i(mny); mxy = wave_max_i(mxy);
+  const bool shifted = mxs - mns < mxx - mnx;
+  const int bx0 = shifted ? mns : mnx, by0 = mny;
+  const int bw = (shifted ? mxs : mxx) + 4 - bx0;
+  int bh = mxy + 4 - by0;
+  // (the limits of the box load's wrap: one step down, two up in x; one each way in y)
+  if ((long long)bw * bh > CAP || bw > 2047 || bh > 1023 || bx0 < -sw || bx0 + bw > 3 * sw || by0 < -sh || by0 + bh > 2 * sh) bh = -1;
+  if (threadIdx.x == 0) tiles[((size_t)blockIdx.z * G.tyN + blockIdx.y) * G.txN + blockIdx.x] = make_int4(bx0, by0, bw, bh);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (lx0 + k < G.fw && ly < G.fh) {
+      const int xk = shifted ? sx[k] + (sx[k] < half ? sw : 0) : sx[k];
+      packed[(size_t)(fy0 + ly) * G.ow + fx0 + lx0 + k] =
+          bh > 0 ? (0x80000000u | ((unsigned)(sy[k] - by0) << 21) | ((unsigned)(xk - bx0) << 10) | (unsigned)fxy[k]) : 0u;
+    }
+}
+
+// one pixel the way k_cubemap renders it: 16 wrapped taps from global memory; B | G << 8 | R << 16
+__device__ __forceinline__ unsigned cubemap_px_gather(const uchar4* __restrict__ src, int sw, int sh, float2 m,
+                                                      const short* __restrict__ tab) {
+  int sx, sy, fxy;
+  remap_coord(m.x, m.y, &sx, &sy, &fxy);
+  const short* w = tab + fxy * 16;
+  int xs[4], ys[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { xs[q] = border_wrap(sx + q, sw); ys[q] = border_wrap(sy + q, sh); }
+  int s0 = 1 << 14, s1 = 1 << 14, s2 = 1 << 14;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uchar4* S = src + (size_t)ys[r] * sw;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uchar4 p = S[xs[q]];
+      const int ww = w[r * 4 + q];
+      s0 += p.x * ww; s1 += p.y * ww; s2 += p.z * ww;
+    }
+  }
+  return (unsigned)sat_u8(s0 >> 15) | ((unsigned)sat_u8(s1 >> 15) << 8) | ((unsigned)sat_u8(s2 >> 15) << 16);
+}
+
+template <int CAP>
+__global__ __launch_bounds__(64) void k_cubemap_tiles(CubeJobs J, int sw, int sh, const float2* __restrict__ maps,
+                                                      const unsigned* __restrict__ packed, const int4* __restrict__ tiles,
+                                                      CubeGeom G, const short* __restrict__ tab) {
+  __shared__ unsigned s_tile[CAP];
+  const TileId tile = xcd_tile();  // x: tile column of the face, y: face slot * tyN + tile row, z: 2 * frame slot + eye
+  const int s = tile.y / G.tyN, ty = tile.y - s * G.tyN;
+  const uchar4* __restrict__ src = J.eye[tile.z];
+  uint8_t* __restrict__ out = J.out[tile.z >> 1] + (size_t)(tile.z & 1) * G.eyeH * G.ow * 3;
+  int fx0, fy0, list;
+  cube_face_slot(G, s, &fx0, &fy0, &list);
+  const int4 box = tiles[((size_t)s * G.tyN + ty) * G.txN + tile.x];  // (uniform)
+  const int bx0 = box.x, by0 = box.y, bw = box.z, bh = box.w;
+  const int lx0 = tile.x * CT_W + (threadIdx.x & 3) * 4, ly = ty * CT_H + (threadIdx.x >> 2);
+  const bool vec = (G.fw & 3) == 0;  // then a thread's four pixels are all inside the face or all outside, and dword-aligned
+  const bool rowIn = ly < G.fh && lx0 < G.fw;
+  const size_t opx = (size_t)(fy0 + ly) * G.ow + fx0 + lx0;
+  unsigned pk[4] = {0u, 0u, 0u, 0u};
+  if (bh > 0) {
+    if (rowIn) {
+      if (vec) {
+        const uint4 p4 = *reinterpret_cast<const uint4*>(packed + opx);
+        pk[0] = p4.x; pk[1] = p4.y; pk[2] = p4.z; pk[3] = p4.w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (lx0 + k < G.fw) pk[k] = packed[opx + k];
+      }
+    }
+    // the tile's source box, wrapped into the eye in x and y (BORDER_WRAP), four rows in flight per thread
+    const unsigned* S32 = reinterpret_cast<const unsigned*>(src);
+    for (int r0 = threadIdx.x >> 5; r0 < bh; r0 += 8)
+      for (int c0 = threadIdx.x & 31; c0 < bw; c0 += 32) {
+        int gx = bx0 + c0;
+        if (gx < 0) gx += sw;
+        if (gx >= sw) gx -= sw;
+        if (gx >= sw) gx -= sw;
+        unsigned v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int r = r0 + 2 * j;
+          int gy = by0 + r;
+          if (gy < 0) gy += sh;
+          if (gy >= sh) gy -= sh;
+          v[j] = r < bh ? S32[(size_t)gy * sw + gx] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int r = r0 + 2 * j;
+          if (r < bh) s_tile[r * bw + c0] = v[j];
+        }
+      }
+    __syncthreads();
+  }
+  unsigned o[4] = {0u, 0u, 0u, 0u};  // B | G << 8 | R << 16
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (!rowIn || lx0 + k >= G.fw) continue;
+    if (bh > 0) {
+      const int rx = (pk[k] >> 10) & 2047, ry = (pk[k] >> 21) & 1023;
+      const uint4* w4 = reinterpret_cast<const uint4*>(tab + (pk[k] & 1023u) * 16);
+      const uint4 wa = w4[0], wb = w4[1];
+      const unsigned wq[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+      const unsigned* T = s_tile + ry * bw + rx;
+      int acc[3] = {1 << 14, 1 << 14, 1 << 14};
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const unsigned p0 = T[r * bw], p1 = T[r * bw + 1], p2 = T[r * bw + 2], p3 = T[r * bw + 3];
+        const s16x2 w01 = __builtin_bit_cast(s16x2, wq[2 * r]), w23 = __builtin_bit_cast(s16x2, wq[2 * r + 1]);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          const unsigned sel = 0x0c040c00u + ch * 0x00010001u;
+          const s16x2 lo = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(p1, p0, sel));
+          const s16x2 hi = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(p3, p2, sel));
+          acc[ch] = __builtin_amdgcn_sdot2(lo, w01, acc[ch], false);
+          acc[ch] = __builtin_amdgcn_sdot2(hi, w23, acc[ch], false);
+        }
+      }
+      o[k] = (unsigned)sat_u8(acc[0] >> 15) | ((unsigned)sat_u8(acc[1] >> 15) << 8) | ((unsigned)sat_u8(acc[2] >> 15) << 16);
+    } else {  // no compact box (pole rings): per-tap gather through the float map
+      o[k] = cubemap_px_gather(src, sw, sh, maps[cube_map_index(G, list, lx0 + k, ly)], tab);
+    }
+  }
+  if (!rowIn) return;
+  uint8_t* ob = out + opx * 3;
+  if (vec) {  // twelve B,G,R bytes as three dwords (k_pack_bgr_v4)
+    unsigned* o32 = reinterpret_cast<unsigned*>(ob);
+    o32[0] = o[0] | (o[1] << 24);
+    o32[1] = (o[1] >> 8) | (o[2] << 16);
+    o32[2] = (o[2] >> 16) | (o[3] << 8);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (lx0 + k < G.fw) {
+        ob[3 * k] = (uint8_t)o[k];
+        ob[3 * k + 1] = (uint8_t)(o[k] >> 8);
+        ob[3 * k + 2] = (uint8_t)(o[k] >> 16);
+      }
+  }
+}
+
 // four BGRA pixels (16 bytes) in, twelve B,G,R bytes (three dwords) out per thread
 __global__ __launch_bounds__(256) void k_pack_bgr_v4(const uint4* __restrict__ src, size_t n4, unsigned* __restrict__ dst) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1860,6 +2063,53 @@ void launch_cubemap(hipStream_t st, const uchar4* eyeL, const uchar4* eyeR, int 
   const int ow = video ? 3 * fw : fw, oh = video ? 4 * fh : 12 * fh;
   hipLaunchKernelGGL(k_cubemap, dim3(cdiv(ow, 256), oh), dim3(256), 0, st, eyeL, eyeR, sw, sh, maps, fw, fh, video, out, ow,
                      oh, T.bicubic_i);
+}
+static CubeGeom cube_geom(int fw, int fh, int video) {
+  CubeGeom G;
+  G.fw = fw; G.fh = fh; G.video = video;
+  G.ow = video ? 3 * fw : fw;
+  G.eyeH = video ? 2 * fh : 6 * fh;
+  G.txN = (int)cdiv(fw, CT_W);
+  G.tyN = (int)cdiv(fh, CT_H);
+  return G;
+}
+size_t cubemap_tile_count(int fw, int fh) { return (size_t)6 * cdiv(fw, CT_W) * cdiv(fh, CT_H); }
+int cubemap_lds_pixels() {
+  static const int cap = [] {
+    const char* e = std::getenv("S360_CUBEMAP_LDS_PIXELS");
+    return e && std::atoi(e) == 2560 ? 2560 : 4096;
+  }();
+  return cap;
+}
+void launch_cubemap_pack(hipStream_t st, const float2* maps, int sw, int sh, int fw, int fh, int video, int lds_pixels,
+                         unsigned* packed, void* tiles) {
+  const CubeGeom G = cube_geom(fw, fh, video);
+  const dim3 grid(G.txN, G.tyN, 6);
+  if (lds_pixels == 2560)
+    hipLaunchKernelGGL(k_cubemap_pack<2560>, grid, dim3(64), 0, st, maps, sw, sh, G, packed, static_cast<int4*>(tiles));
+  else
+    hipLaunchKernelGGL(k_cubemap_pack<4096>, grid, dim3(64), 0, st, maps, sw, sh, G, packed, static_cast<int4*>(tiles));
+}
+void launch_cubemap_tiles(hipStream_t st, const uchar4* const* eyes, uint8_t* const* outs, int n, int sw, int sh,
+                          const float2* maps, const unsigned* packed, const void* tiles, int fw, int fh, int video,
+                          int lds_pixels, const DevTables& T) {
+  const CubeGeom G = cube_geom(fw, fh, video);
+  for (int i = 0; i < n; i += kCubeMaxSlots) {
+    const int m = std::min(kCubeMaxSlots, n - i);
+    CubeJobs J = {};
+    for (int k = 0; k < m; ++k) {
+      J.eye[2 * k] = eyes[2 * (i + k)];
+      J.eye[2 * k + 1] = eyes[2 * (i + k) + 1];
+      J.out[k] = outs[i + k];
+    }
+    const dim3 grid(G.txN, 6 * G.tyN, 2 * m);
+    if (lds_pixels == 2560)
+      hipLaunchKernelGGL(k_cubemap_tiles<2560>, grid, dim3(64), 0, st, J, sw, sh, maps, packed, static_cast<const int4*>(tiles), G,
+                         T.bicubic_i);
+    else
+      hipLaunchKernelGGL(k_cubemap_tiles<4096>, grid, dim3(64), 0, st, J, sw, sh, maps, packed, static_cast<const int4*>(tiles), G,
+                         T.bicubic_i);
+  }
 }
 void launch_pack_bgr(hipStream_t st, const uchar4* src, int w, int h, uint8_t* dst) {
   const size_t n = (size_t)w * h;

@@ -96,6 +96,19 @@ void launch_flatten(hipStream_t st, const uchar4* base, const uchar4* top, uchar
 // stereo cubemap from the two eye panoramas through cached face warp maps (TRSP:917-935)
 void launch_cubemap(hipStream_t st, const uchar4* eyeL, const uchar4* eyeR, int sw, int sh, const float2* maps, int fw,
                     int fh, int video, uint8_t* out, const DevTables& T);
+// The cubemap of every frame (s360_set_cubemap_output): launch_cubemap_pack turns the float face maps into the stacked
+// layout's own pixel order — `packed`: one dword per pixel of ONE eye's half (ow x oh / 2), `tiles`: cubemap_tile_count x 16
+// bytes — once per (sizes, format); launch_cubemap_tiles renders both eyes of n frames in one launch per kCubeMaxSlots
+// frames: eyes[2 k], eyes[2 k + 1] = BGRA eyes of frame k, outs[k] = its stacked BGR cubemap. lds_pixels (the source box a
+// tile may hold, cubemap_lds_pixels(): 4096, or 2560 with S360_CUBEMAP_LDS_PIXELS=2560) must be the same in both calls.
+constexpr int kCubeMaxSlots = 16;
+size_t cubemap_tile_count(int fw, int fh);
+int cubemap_lds_pixels();
+void launch_cubemap_pack(hipStream_t st, const float2* maps, int sw, int sh, int fw, int fh, int video, int lds_pixels,
+                         unsigned* packed, void* tiles);
+void launch_cubemap_tiles(hipStream_t st, const uchar4* const* eyes, uint8_t* const* outs, int n, int sw, int sh,
+                          const float2* maps, const unsigned* packed, const void* tiles, int fw, int fh, int video,
+                          int lds_pixels, const DevTables& T);
 // pole removal pieces (SR/render/PoleRemoval.cpp:32-188, SR/util/CvUtil.cpp:201-222)
 void launch_remap_by_flow(hipStream_t st, const uchar4* src, int w, int h, const float2* flow, uchar4* dst,
                           const DevTables& T);

@@ -448,6 +448,44 @@ class Context:
         self._ck(lib().s360_frame_cubemap(self.h, int(face_width), int(face_height), fmt.encode(), whc, _p(out)))
         return out
 
+    # ---- the stereo cubemap of every frame of a stream or batch (s360_set_cubemap_output) ----
+    def set_cubemap_output(self, face_width, face_height, fmt="video"):
+        """Every frame rendered from now on also leaves its stereo cubemap (face size 0 = off); fetched per frame and slot
+        with download_cubemap / download_cubemap_png under the equirect's age contract."""
+        self._ck(lib().s360_set_cubemap_output(self.h, int(face_width), int(face_height), fmt.encode()))
+
+    def cubemap_size(self):
+        """(width, height, 3) of the stacked cubemap the next frame will leave."""
+        whc = (C.c_int * 3)()
+        self._ck(lib().s360_frame_cubemap_size(self.h, whc))
+        return whc[0], whc[1], whc[2]
+
+    def download_cubemap(self, age=0, slot=None, out=None):
+        """The cubemap rendered with the frame (age 0: enqueued last, 1: the one before) of the selected or the named slot, BGR.
+        The buffer is sized by the CURRENT setting; a frame rendered under another size has to be fetched before the change."""
+        w, h, _ = self.cubemap_size()
+        if out is None:
+            out = np.empty((h, w, 3), np.uint8)
+        assert out.shape == (h, w, 3) and out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"]
+        if slot is None:
+            self._ck(lib().s360_frame_download_cubemap(self.h, int(age), _p(out)))
+        else:
+            self._ck(lib().s360_frame_download_cubemap_slot(self.h, int(slot), int(age), _p(out)))
+        return out
+
+    def download_cubemap_png(self, age=0, slot=None, out=None):
+        """The same cubemap as the bytes of a complete PNG file (frames rendered with set_png_encode(True))."""
+        cap = int(lib().s360_frame_cubemap_png_bound(self.h))
+        if out is None:
+            out = np.empty(cap, np.uint8)
+        assert out.dtype == np.uint8 and out.ndim == 1 and out.flags["C_CONTIGUOUS"]
+        n = C.c_size_t(0)
+        if slot is None:
+            self._ck(lib().s360_frame_download_cubemap_png(self.h, int(age), _p(out), C.c_size_t(out.size), C.byref(n)))
+        else:
+            self._ck(lib().s360_frame_download_cubemap_png_slot(self.h, int(slot), int(age), _p(out), C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value]
+
     def set_sharpening(self, sharpening):
         """FLAGS_sharpening for the frames rendered from now on (TRSP:56, :901)."""
         self._ck(lib().s360_set_sharpening(self.h, C.c_double(sharpening)))
