@@ -90,6 +90,8 @@ CUBEMAP_SYMBOLS = [
     "s360_set_cubemap_output", "s360_frame_cubemap_size", "s360_frame_download_cubemap", "s360_frame_download_cubemap_slot",
     "s360_frame_cubemap_png_bound", "s360_frame_download_cubemap_png", "s360_frame_download_cubemap_png_slot",
 ]
+# ... and the test taps include/s360_debug.h declares (not part of the API)
+DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
 
 _lib = None
 

@@ -9,6 +9,7 @@
 #include <sstream>
 
 #include "../../include/s360.h"
+#include "../../include/s360_debug.h"
 #include "ctx.hpp"
 #include "isp.hpp"
 #include "render.hpp"
@@ -456,6 +457,39 @@ int s360_debug_flow_levels(s360_ctx* c, const char* alg, const uint8_t* i0, cons
       off += v.size();
     }
     if (n_levels) *n_levels = (int)lv.size();
+  });
+}
+// test tap: PixFlow's entry (downscale, grey and alpha planes) alone on caller-made images of any size
+int s360_debug_entry_downscale(s360_ctx* c, const uint8_t* src, int sw, int sh, int batch, int dw, int dh, int generic,
+                               uint8_t* down_out, float* gray_out, float* alpha_out, int* tiled) {
+  return guard(c, [&] {
+    need(c && src && gray_out && alpha_out, "null argument");
+    need(sw > 0 && sh > 0 && dw > 0 && dh > 0 && batch >= 1 && batch <= kMaxFlows, "bad size");
+    need(!generic || down_out, "the generic pair always stores the image");
+    const size_t ns = (size_t)sw * sh, nd = (size_t)dw * dh, B = batch;
+    c->op_a.ensure(B * ns * 4);
+    c->op_b.ensure(2 * B * nd * 4);  // the image, and the scratch copy of the fallback
+    c->op_c.ensure(2 * B * nd * sizeof(float));
+    c->op_d.ensure(B * sizeof(void*));
+    h2d(c, c->op_a.p, src, B * ns * 4);
+    uchar4* down = c->op_b.as<uchar4>();
+    float* gray = c->op_c.as<float>();
+    float* alpha = gray + B * nd;
+    std::vector<const uchar4*> tab(B);  // (lives until the downloads below have synchronised the stream)
+    if (generic) {
+      launch_resize_cubic_u8c4_generic(c->st, c->op_a.as<uchar4>(), sw, sh, ns, down, dw, dh, nd, batch);
+      launch_gray_alpha(c->st, down, nd, nd, gray, alpha, nd, batch);
+    } else {  // as FlowEngine::compute launches it: the sources through a table of pointers
+      for (size_t b = 0; b < B; ++b) tab[b] = c->op_a.as<uchar4>() + ns * b;
+      h2d(c, c->op_d.p, tab.data(), B * sizeof(void*));
+      S360_HIP(hipMemsetAsync(down, 0x5a, B * nd * 4, c->st));  // (an image that is not stored stays this)
+      launch_entry_downscale(c->st, nullptr, sw, sh, 0, down_out ? down : nullptr, down + B * nd, dw, dh, nd, batch,
+                             c->op_d.as<const uchar4*>(), gray, alpha, nd);
+    }
+    if (down_out) d2h(c, down_out, down, B * nd * 4);
+    d2h(c, gray_out, gray, B * nd * sizeof(float));
+    d2h(c, alpha_out, alpha, B * nd * sizeof(float));
+    if (tiled) *tiled = resize_cubic_u8c4_tiled_fits(sw, sh, dw, dh) ? 1 : 0;
   });
 }
 

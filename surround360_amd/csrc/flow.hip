@@ -165,8 +165,9 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
                  tFinal = gaussian_taps(3, 1.0f);
   {
     ProfScope ps(P, "flow_entry");
-    launch_resize_cubic_u8c4(st, nullptr, w, h, 0, M.down.as<uchar4>(), dw_, dh_, n0, N, imageTab);
-    launch_gray_alpha(st, M.down.as<uchar4>(), n0, n0, M.gray.as<float>(), LA(0), n0, N);
+    // the downscaled image itself is read again only by k_motion (temporal state): stored only then
+    launch_entry_downscale(st, nullptr, w, h, 0, usePrev ? M.down.as<uchar4>() : nullptr, M.down.as<uchar4>(), dw_, dh_, n0, N,
+                           imageTab, M.gray.as<float>(), LA(0), n0);
     launch_sepblur(st, M.gray.as<float>(), LI(0), dw_, dh_, 1, n0, N, tPre);
   }
   {

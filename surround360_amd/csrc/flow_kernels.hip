@@ -10,6 +10,7 @@
 // bilinear gather is two 16-byte loads; flow float2 (fx,fy).
 #include "flow_kernels.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <stdexcept>
@@ -201,6 +202,188 @@ __global__ __launch_bounds__(256) void k_resize_cubic_u8c4_h(const uchar4* __res
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (dx0 + j < dw) Dr[j] = o[j];
+    }
+  }
+}
+
+// The same resize for scales around 2 in both directions (PixFlow's entry downscale, x0.5: 1214x1769 -> 607x884 side crops,
+// 10080x2104 -> 5040x1052 pole images), tiled like k_resize_cubic_u8c4_h. With one thread per output pixel the kernel issues 16
+// scattered 4-byte global loads per pixel and moves under 2 TB/s. Here a 64x16 output tile's source box (at most DS_BH rows of
+// DS_BW pixels, checked by the launcher) goes to LDS in 16-byte pieces, all requested before the first is stored; a thread
+// computes the double-precision coordinates and the taps of its 4 adjacent columns and of its row once and produces those 4
+// pixels (one 16-byte store). The box holds LOGICAL columns bx0 .. and rows by0 .. of the border-replicated image (column c is
+// source column clip(c)), so a tap's position in the box is its unclipped coordinate minus the box origin and the taps of a
+// pixel are 4 consecutive box columns. Where the 4 pixels' first taps are 2 columns apart (always, for an exact halving: the
+// fraction is 0.5 everywhere) their 16 taps per source row are 10 consecutive box columns starting on a 16-byte boundary:
+// two ds_read_b128 and one ds_read_b64 per source row instead of 16 ds_read_b32. Arithmetic as in k_resize_cubic_u8c4, term by
+// term: same bytes.
+// gray / alpha given: k_gray_alpha's arithmetic on the pixel just produced, written by the same thread (the entry's `down`
+// image is read back only by k_gray_alpha and, with temporal state, by k_motion). dst may then be null: the image is not stored.
+constexpr int DS_TW = 64, DS_TH = 16, DS_BW = 136, DS_BH = 36;
+typedef float f32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+__global__ __launch_bounds__(256) void k_resize_cubic_u8c4_tiled(const uchar4* __restrict__ src, int sw, int sh, size_t sbs,
+                                                                 uchar4* __restrict__ dst, int dw, int dh, size_t dbs,
+                                                                 double scx, double scy,
+                                                                 const uchar4* const* __restrict__ src_tab,
+                                                                 float* __restrict__ gray, float* __restrict__ alpha,
+                                                                 size_t pbs) {
+  __shared__ __attribute__((aligned(16))) unsigned s_box[DS_BH][DS_BW];
+  const int tid = threadIdx.x, cx = tid & 15, ry = tid >> 4;
+  const int tx0 = blockIdx.x * DS_TW, ty0 = blockIdx.y * DS_TH;
+  const unsigned* S = reinterpret_cast<const unsigned*>(src_tab ? src_tab[blockIdx.z] : src + sbs * blockIdx.z);
+  // the box: logical columns bx0 (first tap of the tile's first column) .. last tap of its last column, rows likewise
+  int s0, s1, t0, t1;
+  float f;
+  resize_coord(tx0, scx, &s0, &f);
+  resize_coord(min(tx0 + DS_TW - 1, dw - 1), scx, &s1, &f);
+  resize_coord(ty0, scy, &t0, &f);
+  resize_coord(min(ty0 + DS_TH - 1, dh - 1), scy, &t1, &f);
+  const int bx0 = s0 - 1, by0 = t0 - 1;
+  const int np4 = min((s1 - s0 + 7) >> 2, DS_BW / 4), nrows = min(t1 - t0 + 4, DS_BH);  // (never cut: launcher)
+  const int npieces = nrows * np4;
+  constexpr int kIters = (DS_BH * (DS_BW / 4) + 255) / 256;
+  u32x4a4 ld[kIters];
+  // all pieces requested before the first is stored (index clamped, no early-out: see k_sepblur)
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int i = min(tid + it * 256, npieces - 1);
+    const int row = i / np4, gx = bx0 + 4 * (i - row * np4);
+    const unsigned* Sr = S + (size_t)clip_idx(by0 + row, sh) * sw;
+    if (gx >= 0 && gx + 3 < sw) ld[it] = *reinterpret_cast<const u32x4a4*>(Sr + gx);
+    else ld[it] = u32x4a4{Sr[clip_idx(gx, sw)], Sr[clip_idx(gx + 1, sw)], Sr[clip_idx(gx + 2, sw)], Sr[clip_idx(gx + 3, sw)]};
+  }
+#pragma unroll
+  for (int it = 0; it < kIters; ++it) {
+    const int i = tid + it * 256;
+    if (i >= npieces) continue;
+    const int row = i / np4, c4 = i - row * np4;
+    *reinterpret_cast<u32x4*>(&s_box[row][4 * c4]) = u32x4{ld[it].x, ld[it].y, ld[it].z, ld[it].w};  // (one ds_write_b128)
+  }
+  // this thread's 4 columns and its row: first-tap positions in the box and the packed 11-bit taps
+  typedef short s16x2 __attribute__((ext_vector_type(2)));
+  const int dx0 = tx0 + 4 * cx, dy = ty0 + ry;
+  int c[4];
+  s16x2 w01[4], w23[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int sx;
+    float cb[4];
+    resize_coord(min(dx0 + j, dw - 1), scx, &sx, &f);
+    cubic_coeffs(f, cb);
+    int a[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a[k] = sat_s16(cv_round(cb[k] * 2048.f));
+    c[j] = sx - 1 - bx0;
+    w01[j] = __builtin_bit_cast(s16x2, (unsigned)(a[0] & 0xffff) | ((unsigned)a[1] << 16));
+    w23[j] = __builtin_bit_cast(s16x2, (unsigned)(a[2] & 0xffff) | ((unsigned)a[3] << 16));
+  }
+  int r0, ay[4];
+  {
+    int sy;
+    float cb[4];
+    resize_coord(min(dy, dh - 1), scy, &sy, &f);
+    cubic_coeffs(f, cb);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ay[k] = sat_s16(cv_round(cb[k] * 2048.f));
+    r0 = sy - 1 - by0;
+  }
+  __syncthreads();
+  if (dx0 >= dw || dy >= dh) return;
+  const float scale = 1.f / (2048 * 2048);
+  const float b0 = (float)ay[0] * scale, b1 = (float)ay[1] * scale, b2 = (float)ay[2] * scale, b3 = (float)ay[3] * scale;
+  // one output pixel from its 4 x 4 taps p[source row][tap]: horizontal v_perm_b32 + v_dot2 per row and channel, then the
+  // vertical pass of k_resize_cubic_u8c4 (float on SSE2-covered columns, fixed point on the odd tail column)
+  auto pixel = [&](int j, const unsigned (&p)[4][4]) -> unsigned {
+    const bool sse = dx0 + j < (dw & ~1);
+    unsigned o = 0;
+#pragma unroll
+    for (int ch = 0; ch < 4; ++ch) {
+      const unsigned sel = 0x0c040c00u + ch * 0x00010001u;
+      int hh[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const s16x2 lo = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(p[r][1], p[r][0], sel));
+        const s16x2 hi = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(p[r][3], p[r][2], sel));
+        hh[r] = __builtin_amdgcn_sdot2(lo, w01[j], 0, false);
+        hh[r] = __builtin_amdgcn_sdot2(hi, w23[j], hh[r], false);
+      }
+      int v;
+      if (sse) {
+        float s = (float)hh[0] * b0;
+        s = s + (float)hh[1] * b1;
+        s = s + (float)hh[2] * b2;
+        s = s + (float)hh[3] * b3;
+        v = cv_round(s);
+      } else {  // |h| < 2^20, |a| < 2^12
+        v = (__mul24(hh[0], ay[0]) + __mul24(hh[1], ay[1]) + __mul24(hh[2], ay[2]) + __mul24(hh[3], ay[3]) + (1 << 21)) >> 22;
+      }
+      o |= (unsigned)sat_u8(v) << (8 * ch);
+    }
+    return o;
+  };
+  unsigned o[4];
+  if (c[1] == c[0] + 2 && c[2] == c[0] + 4 && c[3] == c[0] + 6 && (c[0] & 3) == 0) {
+    unsigned t[4][10];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const unsigned* row = &s_box[r0 + r][c[0]];
+      const u32x4 q0 = *reinterpret_cast<const u32x4*>(row), q1 = *reinterpret_cast<const u32x4*>(row + 4);
+      typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+      const u32x2 q2 = *reinterpret_cast<const u32x2*>(row + 8);
+      t[r][0] = q0.x; t[r][1] = q0.y; t[r][2] = q0.z; t[r][3] = q0.w;
+      t[r][4] = q1.x; t[r][5] = q1.y; t[r][6] = q1.z; t[r][7] = q1.w;
+      t[r][8] = q2.x; t[r][9] = q2.y;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned p[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p[r][k] = t[r][2 * j + k];
+      o[j] = pixel(j, p);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      unsigned p[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) p[r][k] = s_box[r0 + r][c[j] + k];
+      o[j] = pixel(j, p);
+    }
+  }
+  const size_t off = (size_t)dy * dw + dx0;
+  const bool whole = dx0 + 3 < dw;
+  if (dst) {
+    unsigned* Dr = reinterpret_cast<unsigned*>(dst + dbs * blockIdx.z) + off;
+    if (whole) {
+      *reinterpret_cast<u32x4a4*>(Dr) = u32x4a4{o[0], o[1], o[2], o[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (dx0 + j < dw) Dr[j] = o[j];
+    }
+  }
+  if (gray) {  // k_gray_alpha on the pixel just produced
+    const float inv255 = (float)(1.0 / 255.0);
+    float g[4], a[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int gi = (int)((o[j] & 0xff) * 1868 + ((o[j] >> 8) & 0xff) * 9617 + ((o[j] >> 16) & 0xff) * 4899 + (1 << 13)) >> 14;
+      g[j] = (float)gi * inv255;
+      a[j] = (float)(o[j] >> 24) * inv255;
+    }
+    float* Gr = gray + pbs * blockIdx.z + off;
+    float* Ar = alpha + pbs * blockIdx.z + off;
+    if (whole) {
+      *reinterpret_cast<f32x4a4*>(Gr) = f32x4a4{g[0], g[1], g[2], g[3]};
+      *reinterpret_cast<f32x4a4*>(Ar) = f32x4a4{a[0], a[1], a[2], a[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (dx0 + j < dw) { Gr[j] = g[j]; Ar[j] = a[j]; }
     }
   }
 }
@@ -902,6 +1085,21 @@ bool known_result_enabled() {
 
 static inline dim3 grid2d(int w, int h, int B, dim3 blk) { return dim3((w + blk.x - 1) / blk.x, (h + blk.y - 1) / blk.y, B); }
 
+// k_resize_cubic_u8c4_tiled takes a resize when both scales are around 2 and a tile's source box fits: the first taps of a
+// tile's first and last column (row) lie at most ceil((n - 1) * scale) + 1 apart (+ 1: the coordinate is rounded to float
+// before its floor is taken), and the last column's taps end 3 behind its first.
+bool resize_cubic_u8c4_tiled_fits(int sw, int sh, int dw, int dh) {
+  const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
+  return scx >= 1.5 && scy >= 1.5 && (int)std::ceil((std::min(dw, DS_TW) - 1) * scx) + 5 <= DS_BW &&
+         (int)std::ceil((std::min(dh, DS_TH) - 1) * scy) + 5 <= DS_BH;
+}
+void launch_resize_cubic_u8c4_generic(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* dst, int dw,
+                                      int dh, size_t dbs, int B, const uchar4* const* src_tab) {
+  const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
+  dim3 blk(32, 8);
+  hipLaunchKernelGGL(k_resize_cubic_u8c4, grid2d(dw, dh, B, blk), blk, 0, st, src, sw, sh, sbs, dst, dw, dh, dbs, scx,
+                     scy, src_tab);
+}
 void launch_resize_cubic_u8c4(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* dst, int dw,
                               int dh, size_t dbs, int B, const uchar4* const* src_tab) {
   const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
@@ -912,9 +1110,26 @@ void launch_resize_cubic_u8c4(hipStream_t st, const uchar4* src, int sw, int sh,
                        src, sw, sh, sbs, dst, dw, dbs, scx);
     return;
   }
-  dim3 blk(32, 8);
-  hipLaunchKernelGGL(k_resize_cubic_u8c4, grid2d(dw, dh, B, blk), blk, 0, st, src, sw, sh, sbs, dst, dw, dh, dbs, scx,
-                     scy, src_tab);
+  if (resize_cubic_u8c4_tiled_fits(sw, sh, dw, dh)) {
+    hipLaunchKernelGGL(k_resize_cubic_u8c4_tiled, dim3((dw + DS_TW - 1) / DS_TW, (dh + DS_TH - 1) / DS_TH, B), dim3(256), 0, st,
+                       src, sw, sh, sbs, dst, dw, dh, dbs, scx, scy, src_tab, (float*)nullptr, (float*)nullptr, (size_t)0);
+    return;
+  }
+  launch_resize_cubic_u8c4_generic(st, src, sw, sh, sbs, dst, dw, dh, dbs, B, src_tab);
+}
+// PixFlow's entry (PixFlow.h:98-135): the downscaled image's grey and alpha planes; the image itself only where `down` is given.
+// Where the tiled resize does not fit, the generic resize writes the image to `scratch` and k_gray_alpha reads it back.
+void launch_entry_downscale(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* down, uchar4* scratch, int dw,
+                            int dh, size_t dbs, int B, const uchar4* const* src_tab, float* gray, float* alpha, size_t pbs) {
+  if (resize_cubic_u8c4_tiled_fits(sw, sh, dw, dh)) {
+    const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
+    hipLaunchKernelGGL(k_resize_cubic_u8c4_tiled, dim3((dw + DS_TW - 1) / DS_TW, (dh + DS_TH - 1) / DS_TH, B), dim3(256), 0, st,
+                       src, sw, sh, sbs, down, dw, dh, dbs, scx, scy, src_tab, gray, alpha, pbs);
+    return;
+  }
+  uchar4* d = down ? down : scratch;
+  launch_resize_cubic_u8c4_generic(st, src, sw, sh, sbs, d, dw, dh, dbs, B, src_tab);
+  launch_gray_alpha(st, d, (size_t)dw * dh, dbs, gray, alpha, pbs, B);
 }
 void launch_gray_alpha(hipStream_t st, const uchar4* src, size_t n, size_t sbs, float* gray, float* alpha, size_t pbs,
                        int B) {

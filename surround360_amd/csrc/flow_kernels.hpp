@@ -37,6 +37,15 @@ extern unsigned long long g_known_stats[2];
 // live in one allocation); likewise dst_tab / src_tab of the other launchers that take one.
 void launch_resize_cubic_u8c4(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* dst, int dw,
                               int dh, size_t dbs, int B, const uchar4* const* src_tab = nullptr);
+// the one-thread-per-pixel kernel whatever the shape (launch_resize_cubic_u8c4's fallback; the tests' second opinion)
+void launch_resize_cubic_u8c4_generic(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* dst, int dw,
+                                      int dh, size_t dbs, int B, const uchar4* const* src_tab = nullptr);
+// true when the tiled kernel for scales around 2 (a tile's source box in LDS) takes this resize
+bool resize_cubic_u8c4_tiled_fits(int sw, int sh, int dw, int dh);
+// PixFlow's entry: resize + grey and alpha planes of the resized image by the same thread. down == nullptr: the resized image
+// is not stored (scratch, B x dbs pixels, is written only where the tiled kernel does not fit)
+void launch_entry_downscale(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* down, uchar4* scratch, int dw,
+                            int dh, size_t dbs, int B, const uchar4* const* src_tab, float* gray, float* alpha, size_t pbs);
 void launch_gray_alpha(hipStream_t st, const uchar4* src, size_t n, size_t sbs, float* gray, float* alpha, size_t pbs,
                        int B);
 void launch_motion(hipStream_t st, const uchar4* cur, const uchar4* prev, size_t n, size_t sbs, float* motion,

@@ -168,6 +168,18 @@ class Context:
                                               C.c_size_t(cap), C.byref(n)))
         return buf, n.value
 
+    def debug_entry_downscale(self, src, dw, dh, generic=False, keep_down=True):
+        """PixFlow's entry on a stack of BGRA images: (resized images or None, grey planes, alpha planes, tiled kernel taken)."""
+        src = _u8(src)
+        b, sh, sw = src.shape[:3]
+        down = np.empty((b, dh, dw, 4), np.uint8) if keep_down else None
+        gray = np.empty((b, dh, dw), np.float32)
+        alpha = np.empty((b, dh, dw), np.float32)
+        tiled = C.c_int()
+        self._ck(lib().s360_debug_entry_downscale(self.h, _p(src), sw, sh, b, dw, dh, 1 if generic else 0, _p(down), _p(gray),
+                                                  _p(alpha), C.byref(tiled)))
+        return down, gray, alpha, bool(tiled.value)
+
     def spherical_warp_map(self, cam, dw, dh, l, r, t, b):
         m = np.empty((dh, dw, 2), np.float32)
         self._ck(lib().s360_spherical_warp_map(self.h, _p(m), dw, dh, C.byref(cam), C.c_float(l), C.c_float(r),

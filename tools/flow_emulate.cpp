@@ -7,6 +7,7 @@
 
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../surround360_amd/csrc/flow.hpp"
 
@@ -64,6 +65,43 @@ extern "C" int emu_resize_linear_planes(const float* src, int sw, int sh, int B,
 extern "C" int emu_resize_cubic_u8c4(const uint8_t* src, int sw, int sh, int B, int dw, int dh, uint8_t* dst) {
   try {
     launch_resize_cubic_u8c4(nullptr, (const uchar4*)src, sw, sh, (size_t)sw * sh, (uchar4*)dst, dw, dh, (size_t)dw * dh, B);
+    return 0;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+
+// The same resize by the one-thread-per-pixel kernel whatever the shape (the tiled kernels' second opinion).
+extern "C" int emu_resize_cubic_u8c4_generic(const uint8_t* src, int sw, int sh, int B, int dw, int dh, uint8_t* dst) {
+  try {
+    launch_resize_cubic_u8c4_generic(nullptr, (const uchar4*)src, sw, sh, (size_t)sw * sh, (uchar4*)dst, dw, dh, (size_t)dw * dh, B);
+    return 0;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+// PixFlow's entry downscale with the grey and alpha planes (B x dh x dw floats each) from the same launch; down == nullptr: the
+// resized image is not stored. by_table: the sources are passed as a table of B pointers, as FlowEngine does. Returns 1 when the
+// tiled kernel took the shape, 0 when the generic resize and k_gray_alpha did.
+extern "C" int emu_entry_downscale(const uint8_t* src, int sw, int sh, int B, int dw, int dh, uint8_t* down, float* gray,
+                                   float* alpha, int by_table) {
+  try {
+    const size_t ns = (size_t)sw * sh, nd = (size_t)dw * dh;
+    std::vector<const uchar4*> tab(B);
+    for (int b = 0; b < B; ++b) tab[b] = (const uchar4*)src + ns * b;
+    DevBuf scratch;
+    scratch.ensure(B * nd * sizeof(uchar4));
+    launch_entry_downscale(nullptr, by_table ? nullptr : (const uchar4*)src, sw, sh, by_table ? 0 : ns, (uchar4*)down,
+                           scratch.as<uchar4>(), dw, dh, nd, B, by_table ? tab.data() : nullptr, gray, alpha, nd);
+    return resize_cubic_u8c4_tiled_fits(sw, sh, dw, dh) ? 1 : 0;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+// k_gray_alpha on B images of n pixels.
+extern "C" int emu_gray_alpha(const uint8_t* src, size_t n, int B, float* gray, float* alpha) {
+  try {
+    launch_gray_alpha(nullptr, (const uchar4*)src, n, n, gray, alpha, n, B);
     return 0;
   } catch (const std::exception&) {
     return -1;
