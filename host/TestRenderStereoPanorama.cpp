@@ -60,6 +60,11 @@ struct Flags {
          // (s360_set_png_encode / s360_frame_download_png) and this program only writes the bytes; false: the frame's pixels come
          // back and host threads encode them (png_io.hpp). Same pixels in the file either way.
          {"device_png", "true"},
+         // --device_state_png (default off; S360_DEVICE_STATE_PNG=1 in the environment switches it on too, for a per-frame caller
+         // that cannot be changed): the state IMAGES behind a stream's last frame are encoded on the GPU that holds them — one
+         // batched launch sequence per context (s360_frame_encode_state_pngs) — and this program only writes the files' bytes;
+         // off: their pixels come back raw and host threads deflate them (png_io.hpp). Same pixels in the files either way.
+         {"device_state_png", "false"},
          // --num_gpus G: the 14 side pairs of the frame sharded over G GPUs, one RCCL strip gather
          {"num_gpus", "1"},
          // --num_frames N: frames frame_number .. +N-1 as ONE stream in this process (temporal state stays on the
@@ -85,7 +90,7 @@ struct Flags {
   }
   static bool is_bool(const std::string& k) {
     static const char* b[] = {"save_debug_images", "enable_top", "enable_bottom", "enable_pole_removal", "logtostderr",
-                              "alsologtostderr", "write_state", "soft_isp", "device_png"};
+                              "alsologtostderr", "write_state", "soft_isp", "device_png", "device_state_png"};
     for (auto s : b)
       if (k == s) return true;
     return false;
@@ -519,16 +524,35 @@ void render_frame(const Job& J, bool usePrev) {
 
 // state for the next frame: always written by the reference (TRSP:201-208, 247-255, 413-416, 451-452). Fetched from the device
 // in order, PNG-coded / written by a pool of threads (36 images and 32 flow files per 8K frame: 2 GB).
+// --device_state_png: the images are encoded where they lie, one batched encode per context enqueued up front (a pair on the rank
+// of its partition, a pole unit on its owner, the pole-removal images on the bottom GPU), and the pool only writes bytes.
+struct StateTimes { double images = 0, flows = 0, writers = 0; };  // host-thread seconds: fetching images / flows, waiting for the pool
+StateTimes g_stateTimes;
+bool device_state_png(const Flags& F) {
+  const char* e = std::getenv("S360_DEVICE_STATE_PNG");
+  return F.b("device_state_png") || (e && !std::strcmp(e, "1"));
+}
 void write_state(const Job& J, const std::string& frame) {
   const std::string outData = J.F.s("output_data_dir");
   const std::string flowDir = outData + "/flow/" + frame, flowImagesDir = outData + "/debug/" + frame + "/flow_images";
   mkdirs(flowDir);
   mkdirs(flowImagesDir);
-  struct Item { std::string path; std::vector<uint8_t> img; std::vector<float> fl; int w = 0, h = 0; };
-  TaskQueue coders(state_workers());  // (joined when this function returns: every file is complete then)
+  const bool devState = device_state_png(J.F);
+  double tImages = 0, tFlows = 0;
+  struct Item {
+    std::string path; std::vector<uint8_t> img; std::vector<float> fl; int w = 0, h = 0;
+    std::unique_ptr<uint8_t[]> file; size_t fileBytes = 0;  // a finished file (its buffer has the file's BOUND and is not zero-filled: only the pages the file reaches are touched)
+  };
+  struct DevImage { s360_ctx* c; std::string what; int idx; std::string path; };
+  std::vector<DevImage> devImages;  // (--device_state_png) in the order the images are asked for
+  const double t00 = now_sec();
+  auto coders = std::make_unique<TaskQueue>(state_workers());  // (joined before this function returns: every file is complete then)
+  bool flowsNow = false;  // (get_flow: fetch now, do not defer)
   auto hand_over = [&](std::shared_ptr<Item> it) {
-    coders.push([it] {
-      if (!it->img.empty()) {
+    coders->push([it] {
+      if (it->file) {
+        save_bytes(it->path, it->file.get(), it->fileBytes);
+      } else if (!it->img.empty()) {
         try {
           // (the pool is the parallelism; only the pole units' 85 MB images get deflate threads of their own)
           pngio::write(it->path, it->img.data(), it->w, it->h, 4, 1, it->img.size() > ((size_t)32 << 20) ? 4 : 1);
@@ -541,6 +565,8 @@ void write_state(const Job& J, const std::string& frame) {
     });
   };
   auto get_img = [&](s360_ctx* c, const char* what, int idx, const std::string& path) {
+    if (devState) { devImages.push_back({c, what, idx, path}); return; }
+    const double t0 = now_sec();
     int whc[3];
     ck(s360_frame_get_u8(c, what, idx, whc, nullptr), c);
     auto it = std::make_shared<Item>();
@@ -548,8 +574,14 @@ void write_state(const Job& J, const std::string& frame) {
     it->img.resize((size_t)whc[0] * whc[1] * 4);
     ck(s360_frame_get_u8(c, what, idx, whc, it->img.data()), c);
     hand_over(std::move(it));
+    tImages += now_sec() - t0;
   };
+  struct DevFlow { s360_ctx* c; std::string what; int idx; std::string path; };
+  std::vector<DevFlow> laterFlows;  // (--device_state_png) the flows follow the images: their fetch waits for the context's stream
   auto get_flow = [&](s360_ctx* c, const char* what, int idx, const std::string& path) {
+    if (devState && !flowsNow) { laterFlows.push_back({c, what, idx, path}); return; }
+    const double t0 = now_sec();
+    struct Add { double& t; double t0; ~Add() { t += now_sec() - t0; } } add{tFlows, t0};
     int whc[3];
     ck(s360_frame_get_f32(c, what, idx, whc, nullptr), c);
     auto it = std::make_shared<Item>();
@@ -581,6 +613,37 @@ void write_state(const Job& J, const std::string& frame) {
       get_flow(c, "flow_r_to_l", i, flowDir + "/flowRtoL_" + std::to_string(i) + ".bin");
     }
   }
+  if (devState) {
+    const double t0 = now_sec();
+    // one batched encode per context, all of them enqueued before the first file is fetched
+    std::vector<s360_ctx*> ctxs;
+    for (const DevImage& d : devImages)
+      if (std::find(ctxs.begin(), ctxs.end(), d.c) == ctxs.end()) ctxs.push_back(d.c);
+    std::vector<std::vector<size_t>> mine(ctxs.size());
+    for (size_t k = 0; k < ctxs.size(); ++k) {
+      std::vector<const char*> names;
+      std::vector<int> idx;
+      for (size_t j = 0; j < devImages.size(); ++j)
+        if (devImages[j].c == ctxs[k]) { mine[k].push_back(j); names.push_back(devImages[j].what.c_str()); idx.push_back(devImages[j].idx); }
+      ck(s360_frame_encode_state_pngs(ctxs[k], (int)names.size(), names.data(), idx.data()), ctxs[k]);
+    }
+    for (size_t k = 0; k < ctxs.size(); ++k)
+      for (size_t i = 0; i < mine[k].size(); ++i) {
+        auto it = std::make_shared<Item>();
+        it->path = devImages[mine[k][i]].path;
+        const size_t cap = s360_frame_state_png_bound(ctxs[k], (int)i);
+        it->file.reset(new uint8_t[cap]);
+        ck(s360_frame_download_state_png(ctxs[k], (int)i, it->file.get(), cap, &it->fileBytes), ctxs[k]);
+        hand_over(std::move(it));
+      }
+    tImages += now_sec() - t0;
+    flowsNow = true;
+    for (const DevFlow& f : laterFlows) get_flow(f.c, f.what.c_str(), f.idx, f.path);
+  }
+  coders.reset();
+  g_stateTimes.images += tImages;
+  g_stateTimes.flows += tFlows;
+  g_stateTimes.writers += now_sec() - t00 - tImages - tFlows;
 }
 
 // "000123" + 1 -> "000124" (same width); frame names of the reference's datasets are zero-padded decimal numbers
@@ -895,6 +958,10 @@ static int run_job(const Flags& flags) {
     if (numFrames == 1) {
       std::fprintf(stderr, "GPU render + download:   %.3f  (%d GPU%s)\n", renderEnd - renderStart, G, G > 1 ? "s, RCCL strip gather" : "");
       std::fprintf(stderr, "state files:             %.3f  (beside the equirect's PNG encoder)\n", stateEnd - renderEnd);
+      std::fprintf(stderr, "state files, images:     %.3f  (%s)\n", g_stateTimes.images,
+                   device_state_png(F) ? "encoded on the device, fetched as files" : "fetched raw, deflated by the writers");
+      std::fprintf(stderr, "state files, flows:      %.3f  (fetched)\n", g_stateTimes.flows);
+      std::fprintf(stderr, "state files, writers:    %.3f  (waiting for the pool to finish the files)\n", g_stateTimes.writers);
       std::fprintf(stderr, "equirect PNG encode:     %.3f  (what was left of it)\n", endTime - stateEnd);
     } else {
       std::fprintf(stderr, "stream of %d frames:      %.3f  (%.3f per frame: decode, upload, render, download, encode overlapped)\n",

@@ -90,6 +90,11 @@ CUBEMAP_SYMBOLS = [
     "s360_set_cubemap_output", "s360_frame_cubemap_size", "s360_frame_download_cubemap", "s360_frame_download_cubemap_slot",
     "s360_frame_cubemap_png_bound", "s360_frame_download_cubemap_png", "s360_frame_download_cubemap_png_slot",
 ]
+# ... and every symbol include/s360_state_png.h declares (RGBA and batched PNG encode; s360.h includes that header too)
+STATE_PNG_SYMBOLS = [
+    "s360_png_bound_c", "s360_encode_png_c", "s360_encode_png_batch",
+    "s360_frame_encode_state_pngs", "s360_frame_state_png_bound", "s360_frame_download_state_png",
+]
 # ... and the test taps include/s360_debug.h declares (not part of the API)
 DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
 
@@ -122,6 +127,19 @@ def lib():
         L.s360_png_bound.restype = C.c_size_t
         L.s360_png_bound.argtypes = [C.c_int, C.c_int]
         L.s360_host_free.argtypes = [C.c_void_p]
+        L.s360_png_bound_c.restype = C.c_size_t
+        L.s360_png_bound_c.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.s360_encode_png_c.restype = C.c_int
+        L.s360_encode_png_c.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.s360_encode_png_batch.restype = C.c_int
+        L.s360_encode_png_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.s360_frame_encode_state_pngs.restype = C.c_int
+        L.s360_frame_encode_state_pngs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int)]
+        L.s360_frame_state_png_bound.restype = C.c_size_t
+        L.s360_frame_state_png_bound.argtypes = [C.c_void_p, C.c_int]
+        L.s360_frame_download_state_png.restype = C.c_int
+        L.s360_frame_download_state_png.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.s360_isp_config_defaults.restype = None
         L.s360_isp_destroy.restype = None
         L.s360_isp_destroy.argtypes = [C.c_void_p]

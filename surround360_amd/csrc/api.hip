@@ -68,11 +68,11 @@ static int guard(s360_ctx* c, F&& f) {
 // they wait: f receives the held lock and may unlock / relock it around the wait, so that another host thread can feed
 // the next frame meanwhile (a stream's uploader beside the thread that fetches and encodes).
 template <typename F>
-static int guard_l(s360_ctx* c, F&& f) {
+static int guard_l(s360_ctx* c, F&& f, bool needs_frame = true /* false: operator-level calls work on a context whose flags describe no frame */) {
   std::unique_lock<std::recursive_mutex> lk(c->mu);
   try {
     c->make_current();
-    if (!c->frame_invalid.empty()) throw Error(S360_ERR_INVALID_ARG, c->frame_invalid);
+    if (needs_frame && !c->frame_invalid.empty()) throw Error(S360_ERR_INVALID_ARG, c->frame_invalid);
     f(lk);
     if (!lk.owns_lock()) lk.lock();
     return S360_OK;
@@ -323,6 +323,11 @@ void s360_destroy(s360_ctx* c) {
   if (c->evDown) (void)hipEventDestroy(c->evDown);
   if (c->downErr) (void)hipHostFree(c->downErr);
   if (c->pngMetaHost) (void)hipHostFree(c->pngMetaHost);
+  for (s360_ctx::PngBatch* B : {&c->statePng, &c->opPng}) {
+    if (B->tabHost) (void)hipHostFree(B->tabHost);
+    if (B->metaHost) (void)hipHostFree(B->metaHost);
+    if (B->events) { (void)hipEventDestroy(B->evEnc); (void)hipEventDestroy(B->evRead); (void)hipEventDestroy(B->evAfter); }
+  }
   if (c->evUpHost) (void)hipEventDestroy(c->evUpHost);
   if (c->stUp) {
     (void)hipStreamDestroy(c->stUp);
@@ -1249,60 +1254,232 @@ int s360_frame_cubemap(s360_ctx* c, int face_w, int face_h, const char* format, 
     d2h(c, out_bgr, frame_state(c).cubeOut.p, (size_t)ow * oh * 3);
   });
 }
+// Where the named 8-bit intermediate of the selected slot's latest frame lies on the device (the names of s360_frame_get_u8).
+// `pack_eye`: eye_l / eye_r are packed to B,G,R into op_f (the caller wants their pixels, not only their size).
+static const void* frame_u8_source(s360_ctx* c, FrameState& F, const std::string& n, int idx, bool pack_eye, int& w, int& h, int& ch) {
+  const s360_geometry& g = c->g;
+  const int W = c->P.eqr_width, H = c->P.eqr_height, P = F.P;
+  const void* src = nullptr;
+  w = 0; h = 0; ch = 4;
+  const int nloc = F.side_p1 - F.side_p0;
+  if (n == "projection") {
+    need(idx >= 0 && idx < P && F.sc->proj.p, "projection not available");
+    w = g.cam_image_width; h = g.cam_image_height;
+    src = F.sc->proj.as<uchar4>() + (size_t)w * h * idx;
+  } else if (n == "overlap_l" || n == "overlap_r") {
+    need(idx >= F.side_p0 && idx < F.side_p1 && F.overlaps[F.last_side].p, "overlap not available");
+    w = g.overlap_image_width; h = g.cam_image_height;
+    const int j = idx - F.side_p0 + (n == "overlap_r" ? nloc : 0);
+    src = F.overlaps[F.last_side].as<uchar4>() + (size_t)w * h * j;
+  } else if (n == "side_pano_l" || n == "side_pano_r") {
+    const int e = n == "side_pano_r";
+    need(F.panoDbg[e].p, "enable keep_intermediates before rendering");
+    w = W; h = H; src = F.panoDbg[e].p;
+  } else if (n == "top_spherical") {
+    need(F.sc->topSph.p, "not available"); w = W; h = g.top_rows; src = F.sc->topSph.p;
+  } else if (n == "bottom_spherical") {
+    need(F.sc->botSph.p, "not available"); w = W; h = g.bottom_rows; src = F.sc->botSph.p;
+  } else if (n == "pole_warped") {
+    need(idx >= 0 && idx < 4 && F.sc->poleWarped[idx].p, "not available"); w = W; h = H; src = F.sc->poleWarped[idx].p;
+  } else if (n == "extended_side" || n == "extended_fisheye") {
+    need(idx >= 0 && idx < 4 && F.extImgs[F.last_pole].p, "not available");
+    w = F.extW; h = idx < 2 ? F.poleRowsT : F.poleRowsB;
+    const int slot = n == "extended_side" ? idx : (idx < 2 ? 4 : 5);
+    src = F.extImgs[F.last_pole].as<uchar4>() + F.extStride * slot;
+  } else if (n == "bottom_image" || n == "bottom_image2") {
+    need(F.prImgs[F.last_pr].p && F.have_prev_pr, "not available (pole removal not run)");
+    w = F.poleW; h = F.poleH;
+    src = F.prImgs[F.last_pr].as<uchar4>() + (n == "bottom_image2" ? (size_t)w * h : 0);
+  } else if (n == "eye_l" || n == "eye_r") {
+    const int e = n == "eye_r";
+    need(F.pano[e].p, "not available");
+    w = W; h = H; ch = 3;
+    if (pack_eye) {
+      c->op_f.ensure((size_t)w * h * 3);
+      wait_finish_stream(c);  // the pack kernel reads the composited panorama
+      launch_pack_bgr(c->st, F.pano[e].as<uchar4>(), w, h, c->op_f.as<uint8_t>());
+      src = c->op_f.p;
+    }
+  } else {
+    throw Error(S360_ERR_INVALID_ARG, "unknown intermediate name: " + n);
+  }
+  return src;
+}
 int s360_frame_get_u8(s360_ctx* c, const char* name, int idx, int whc[3], uint8_t* dst) {
   return frame_guard(c, [&] {
     need(c && name && whc, "bad argument");
-    FrameState& F = frame_state(c);
-    const s360_geometry& g = c->g;
-    const int W = c->P.eqr_width, H = c->P.eqr_height, P = F.P;
-    const std::string n(name);
-    const void* src = nullptr;
     int w = 0, h = 0, ch = 4;
-    const int nloc = F.side_p1 - F.side_p0;
-    if (n == "projection") {
-      need(idx >= 0 && idx < P && F.sc->proj.p, "projection not available");
-      w = g.cam_image_width; h = g.cam_image_height;
-      src = F.sc->proj.as<uchar4>() + (size_t)w * h * idx;
-    } else if (n == "overlap_l" || n == "overlap_r") {
-      need(idx >= F.side_p0 && idx < F.side_p1 && F.overlaps[F.last_side].p, "overlap not available");
-      w = g.overlap_image_width; h = g.cam_image_height;
-      const int j = idx - F.side_p0 + (n == "overlap_r" ? nloc : 0);
-      src = F.overlaps[F.last_side].as<uchar4>() + (size_t)w * h * j;
-    } else if (n == "side_pano_l" || n == "side_pano_r") {
-      const int e = n == "side_pano_r";
-      need(F.panoDbg[e].p, "enable keep_intermediates before rendering");
-      w = W; h = H; src = F.panoDbg[e].p;
-    } else if (n == "top_spherical") {
-      need(F.sc->topSph.p, "not available"); w = W; h = g.top_rows; src = F.sc->topSph.p;
-    } else if (n == "bottom_spherical") {
-      need(F.sc->botSph.p, "not available"); w = W; h = g.bottom_rows; src = F.sc->botSph.p;
-    } else if (n == "pole_warped") {
-      need(idx >= 0 && idx < 4 && F.sc->poleWarped[idx].p, "not available"); w = W; h = H; src = F.sc->poleWarped[idx].p;
-    } else if (n == "extended_side" || n == "extended_fisheye") {
-      need(idx >= 0 && idx < 4 && F.extImgs[F.last_pole].p, "not available");
-      w = F.extW; h = idx < 2 ? F.poleRowsT : F.poleRowsB;
-      const int slot = n == "extended_side" ? idx : (idx < 2 ? 4 : 5);
-      src = F.extImgs[F.last_pole].as<uchar4>() + F.extStride * slot;
-    } else if (n == "bottom_image" || n == "bottom_image2") {
-      need(F.prImgs[F.last_pr].p && F.have_prev_pr, "not available (pole removal not run)");
-      w = F.poleW; h = F.poleH;
-      src = F.prImgs[F.last_pr].as<uchar4>() + (n == "bottom_image2" ? (size_t)w * h : 0);
-    } else if (n == "eye_l" || n == "eye_r") {
-      const int e = n == "eye_r";
-      need(F.pano[e].p, "not available");
-      w = W; h = H; ch = 3;
-      if (dst) {
-        c->op_f.ensure((size_t)w * h * 3);
-        wait_finish_stream(c);  // the pack kernel reads the composited panorama
-        launch_pack_bgr(c->st, F.pano[e].as<uchar4>(), w, h, c->op_f.as<uint8_t>());
-        src = c->op_f.p;
-      }
-    } else {
-      throw Error(S360_ERR_INVALID_ARG, "unknown intermediate name: " + n);
-    }
+    const void* src = frame_u8_source(c, frame_state(c), name, idx, dst != nullptr, w, h, ch);
     whc[0] = w; whc[1] = h; whc[2] = ch;
     if (dst) d2h(c, dst, src, (size_t)w * h * ch);
   });
+}
+/* ---- PNG files of B,G,R and B,G,R,A images, one or many per launch sequence (include/s360_state_png.h) ---- */
+size_t s360_png_bound_c(int w, int h, int channels) {
+  size_t n = 0;
+  (void)guard(nullptr, [&] { n = PngPlan::make(w, h, channels).file_bound; });
+  return n;
+}
+int s360_encode_png_c(s360_ctx* c, const uint8_t* px, int w, int h, int channels, uint8_t* out, size_t cap, size_t* n_out) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard_l(c, [&](std::unique_lock<std::recursive_mutex>& lk) {
+    need(px && out && n_out && w > 0 && h > 0, "bad argument");
+    const PngPlan plan = PngPlan::make(w, h, channels);
+    const size_t nb = (size_t)w * h * channels;
+    c->op_a.ensure((nb + 3) & ~(size_t)3);
+    c->op_b.ensure(plan.file_bound);
+    S360_HIP(hipMemcpyAsync(c->op_a.p, px, nb, hipMemcpyHostToDevice, c->st));
+    png_encode_enqueue(c->st, c->op_a.as<uint8_t>(), plan, c->op_c, c->op_d, c->op_b.as<uint8_t>());
+    S360_HIP(hipStreamSynchronize(c->st));
+    png_fetch(c, lk, plan, c->op_d, c->op_b, nullptr, nullptr, nullptr, out, cap, n_out, false);  // (the operator scratch stays locked)
+  }, false);
+}
+// A batch's plan and its page-locked areas. The table's host copy is rewritten here: the upload of the batch before (a whole encode
+// ago) has left it in any real use; if it has not, this is the one place that waits for it.
+static void png_batch_prepare(s360_ctx* c, s360_ctx::PngBatch& B, const std::vector<PngPlan>& plans) {
+  if (!B.events) {
+    S360_HIP(hipEventCreateWithFlags(&B.evEnc, hipEventDisableTiming));
+    S360_HIP(hipEventCreateWithFlags(&B.evRead, hipEventDisableTiming));
+    S360_HIP(hipEventCreateWithFlags(&B.evAfter, hipEventDisableTiming));
+    B.events = true;
+  }
+  if (B.haveEnc && hipEventQuery(B.evEnc) != hipSuccess) {
+    (void)hipGetLastError();
+    S360_HIP(hipEventSynchronize(B.evEnc));
+  }
+  B.haveEnc = false;
+  B.plan = PngBatchPlan::make(plans);
+  auto grow = [](void*& p, size_t& have, size_t want) {
+    if (have >= want) return;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    have = 0;
+    S360_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
+    have = want;
+  };
+  grow(B.tabHost, B.tabHostBytes, PngBatchPlan::table_bytes(plans.size(), (size_t)B.plan.nbands));
+  grow(B.metaHost, B.metaHostBytes, B.plan.meta_records * sizeof(PngBandMeta));
+}
+// ... and its launch sequence on the context's stream, the band tables' copy to the host behind it. Nothing waits.
+static void png_batch_run(s360_ctx* c, s360_ctx::PngBatch& B, const uint8_t* const* px) {
+  if (B.haveRead) S360_HIP(hipStreamWaitEvent(c->st, B.evRead, 0));  // (a fetch of the batch before may still read its file images)
+  png_batch_enqueue(c->st, px, B.plan, B.table, B.tabHost, B.scratch, B.meta, B.files);
+  S360_HIP(hipMemcpyAsync(B.metaHost, B.meta.p, B.plan.meta_records * sizeof(PngBandMeta), hipMemcpyDeviceToHost, c->st));
+  S360_HIP(hipEventRecord(B.evEnc, c->st));
+  B.haveEnc = true;
+  ++B.gen;
+}
+// File i of the batch into the caller's buffer. Everything the transfer needs is enqueued, and the read-done event recorded, BEFORE
+// the lock is first released; plan, pointers and the batch's generation are taken by value. The file's size is known up front when
+// the band tables have already arrived (the usual case from the second file on); otherwise as much as the caller's buffer or the
+// file's bound allows is copied, and the size is checked afterwards — a buffer that turns out too small is refused, never overrun.
+static void png_batch_fetch(s360_ctx* c, std::unique_lock<std::recursive_mutex>& lk, s360_ctx::PngBatch& B, int i, uint8_t* out, size_t cap,
+                            size_t* n_out, bool release) {
+  if (!B.haveEnc) throw Error(S360_ERR_STATE, "no PNG batch has been encoded");
+  need(i >= 0 && (size_t)i < B.plan.img.size(), "PNG index out of range");
+  need(out && n_out, "bad argument");
+  const PngPlan plan = B.plan.img[(size_t)i];
+  const uint8_t* file = B.files.as<uint8_t>() + B.plan.file_off[(size_t)i];
+  const PngBandMeta* mh = static_cast<const PngBandMeta*>(B.metaHost) + B.plan.meta0[(size_t)i];
+  const unsigned long long gen = B.gen;
+  const char* too_small = "png: output buffer too small (s360_frame_state_png_bound / s360_png_bound_c give the size to allocate)";
+  if (!c->stDown) S360_HIP(hipStreamCreateWithFlags(&c->stDown, hipStreamNonBlocking));
+  std::vector<PngBandMeta> m((size_t)plan.nbands + 1);
+  const bool known = hipEventQuery(B.evEnc) == hipSuccess;
+  if (!known) (void)hipGetLastError();
+  size_t nbytes = std::min(cap, plan.file_bound);
+  if (known) {
+    std::memcpy(m.data(), mh, m.size() * sizeof(PngBandMeta));
+    nbytes = (size_t)m[(size_t)plan.nbands].file_off;
+    if (nbytes > plan.file_bound || nbytes + 28 > cap) throw Error(S360_ERR_INVALID_ARG, too_small);
+  }
+  hipEvent_t ev = nullptr;  // (an event per call: fetches of different files may wait at the same time)
+  S360_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventBlockingSync));
+  struct Drop { hipEvent_t e; ~Drop() { (void)hipEventDestroy(e); } } drop{ev};
+  S360_HIP(hipStreamWaitEvent(c->stDown, B.evEnc, 0));
+  S360_HIP(hipMemcpyAsync(out, file, nbytes, hipMemcpyDeviceToHost, c->stDown));
+  S360_HIP(hipEventRecord(B.evRead, c->stDown));
+  B.haveRead = true;
+  S360_HIP(hipEventRecord(ev, c->stDown));
+  if (release) lk.unlock();
+  const hipError_t rc = hipEventSynchronize(ev);
+  if (release) lk.lock();
+  S360_HIP(rc);
+  if (B.gen != gen) throw Error(S360_ERR_STATE, "the PNG batch was replaced by a later encode while this file was being fetched");
+  if (!known) {
+    std::memcpy(m.data(), mh, m.size() * sizeof(PngBandMeta));
+    const size_t end = (size_t)m[(size_t)plan.nbands].file_off;
+    if (end > plan.file_bound || end + 28 > cap) throw Error(S360_ERR_INVALID_ARG, too_small);
+  }
+  // the file's frame around the bands and the chunks' CRCs: host work on the caller's buffer and on copies, the context stays free
+  if (release) lk.unlock();
+  const size_t n = png_finish_host(out, cap, plan, m.data(), png_crc_threads());
+  if (release) lk.lock();
+  *n_out = n;
+}
+int s360_encode_png_batch(s360_ctx* c, int n, const uint8_t* const* px, const int* w, const int* h, const int* channels, uint8_t* const* out,
+                          const size_t* cap, size_t* n_out) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard_l(c, [&](std::unique_lock<std::recursive_mutex>& lk) {
+    need(n > 0 && n <= 4096 && px && w && h && channels && out && cap && n_out, "bad argument");
+    std::vector<PngPlan> plans;
+    std::vector<size_t> at;
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+      need(px[i] && out[i], "bad argument");
+      plans.push_back(PngPlan::make(w[i], h[i], channels[i]));
+      at.push_back(total);
+      total += ((size_t)w[i] * h[i] * channels[i] + 15) & ~(size_t)15;
+    }
+    c->op_a.ensure(total);
+    std::vector<const uint8_t*> dev;
+    for (int i = 0; i < n; ++i) {
+      dev.push_back(c->op_a.as<uint8_t>() + at[(size_t)i]);
+      S360_HIP(hipMemcpyAsync(c->op_a.as<uint8_t>() + at[(size_t)i], px[i], (size_t)w[i] * h[i] * channels[i], hipMemcpyHostToDevice, c->st));
+    }
+    png_batch_prepare(c, c->opPng, plans);
+    png_batch_run(c, c->opPng, dev.data());
+    S360_HIP(hipStreamSynchronize(c->st));
+    for (int i = 0; i < n; ++i) png_batch_fetch(c, lk, c->opPng, i, out[i], cap[i], &n_out[i], false);  // (the operator scratch stays locked)
+  }, false);
+}
+int s360_frame_encode_state_pngs(s360_ctx* c, int n, const char* const* names, const int* idx) {
+  return frame_guard(c, [&] {
+    need(c && n > 0 && n <= 4096 && names && idx, "bad argument");
+    FrameState& F = frame_state(c);
+    std::vector<PngPlan> plans;
+    std::vector<const uint8_t*> px;
+    for (int i = 0; i < n; ++i) {
+      need(names[i] != nullptr, "bad argument");
+      int w = 0, h = 0, ch = 0;
+      const void* src = frame_u8_source(c, F, names[i], idx[i], false, w, h, ch);
+      need(ch == 4 && src, "only the 4-channel intermediates are encoded as state images");
+      plans.push_back(PngPlan::make(w, h, 4));
+      px.push_back(static_cast<const uint8_t*>(src));
+    }
+    s360_ctx::PngBatch& B = c->statePng;
+    png_batch_prepare(c, B, plans);
+    if (c->st2) {  // frame pipelining: the pole stage's images come from the finish stream — ordered on the device, not by the host
+      S360_HIP(hipEventRecord(B.evAfter, c->st2));
+      S360_HIP(hipStreamWaitEvent(c->st, B.evAfter, 0));
+    }
+    png_batch_run(c, B, px.data());
+  });
+}
+size_t s360_frame_state_png_bound(s360_ctx* c, int i) {
+  size_t n = 0;
+  if (!c) return 0;
+  (void)guard(c, [&] {
+    const s360_ctx::PngBatch& B = c->statePng;
+    if (!B.haveEnc) throw Error(S360_ERR_STATE, "no PNG batch has been encoded");
+    need(i >= 0 && (size_t)i < B.plan.img.size(), "PNG index out of range");
+    n = B.plan.img[(size_t)i].file_bound;
+  });
+  return n;
+}
+int s360_frame_download_state_png(s360_ctx* c, int i, uint8_t* out, size_t cap, size_t* n_out) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard_l(c, [&](std::unique_lock<std::recursive_mutex>& lk) { png_batch_fetch(c, lk, c->statePng, i, out, cap, n_out, true); });
 }
 int s360_frame_get_f32(s360_ctx* c, const char* name, int idx, int whc[3], float* dst) {
   return frame_guard(c, [&] {

@@ -7,6 +7,7 @@
 
 #include "core.hpp"
 #include "flow.hpp"
+#include "png.hpp"
 #include "rig.hpp"
 
 namespace s360 {
@@ -44,6 +45,23 @@ struct s360_ctx {
   bool png_encode = false;       // s360_set_png_encode: every finished frame is also encoded as a PNG on the device
   void* pngMetaHost = nullptr;   // pinned landing area of a frame's band table (s360_frame_download_png)
   size_t pngMetaHostBytes = 0;
+  // A batch of PNG files encoded by one launch sequence (png_batch_enqueue): the state images of a frame
+  // (s360_frame_encode_state_pngs -> statePng) and the operator form (s360_encode_png_batch -> opPng). Buffers are allocated on
+  // first use, grow only, and belong to the context. `gen` counts the encode calls: a fetch that finds another batch after its
+  // wait reports S360_ERR_STATE instead of mixing two batches.
+  struct PngBatch {
+    s360::PngBatchPlan plan;
+    s360::DevBuf table, scratch, meta, files;
+    void* tabHost = nullptr;   // pinned: the table as it is uploaded
+    size_t tabHostBytes = 0;
+    void* metaHost = nullptr;  // pinned: the band tables of all images, copied behind the gather
+    size_t metaHostBytes = 0;
+    hipEvent_t evEnc = nullptr, evRead = nullptr;  // behind the band tables' copy / behind the latest fetch's copy
+    hipEvent_t evAfter = nullptr;                  // frame pipelining: orders the encode behind the finish stream
+    bool haveEnc = false, haveRead = false, events = false;
+    unsigned long long gen = 0;
+  };
+  PngBatch statePng, opPng;
   hipEvent_t evUpHost = nullptr; // s360_frame_uploads_complete
   static constexpr int kPinChunks = 4;
   static constexpr size_t kPinChunkBytes = (size_t)8 << 20;

@@ -37,6 +37,24 @@
 // waiting 0.49 of their time (profiles/r06_v9_png_pmc.txt); phase cuts: pass 1 0.43 ms, code build 0.14, pass 2 0.82. The
 // instruction count fell by 22 % and the time did not: what is left is the workgroup's own critical path — four barriers per tile in
 // pass 2, the one-thread code build, waves of unequal token counts meeting at every barrier — not issue slots and not bytes.
+//
+// Channels. The band kernel is a template on the channel count C: 3 = B,G,R in, 8-bit RGB out (the equirect, the cubemap); 4 =
+// B,G,R,A in, 8-bit RGBA out (colour type 6: bytes 0 and 2 of a pixel swapped, alpha kept, Sub at a distance of 4 bytes, line = 1 + 4 w)
+// — the temporal state images of a frame (overlaps, extended pole images, pole-removal images), which lie as contiguous B,G,R,A in
+// HBM. Only the two byte reads of a lane (its channel, the same channel one pixel to the left) know C; tokens stay distance-1 byte
+// matches, the tile stays 12288 bytes (4096 or 3072 pixels; with C = 4 a 64-byte group is 16 whole pixels, four lanes share an LDS
+// dword and the reads are conflict-free), Smem and the per-wave bit regions keep their size, the band rule stays one on bytes.
+// Batch. C = 0 is the kernel over the bands of MANY images of differing size and channel count (png_batch_enqueue): a device table
+// holds one descriptor per image and the image index of every band, a workgroup looks its band up and runs the C = 3 or C = 4 body.
+// One band launch, one layout launch (a workgroup per image: the prefix sum is segmented), one gather launch; every image gets a
+// file image and a band table of its own; a band is a workgroup that lives for its own rows only, so a small image's band never
+// holds a CU longer than its own work.
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage; LDS 53 816 B per workgroup of 512 threads, no scratch, no AGPRs):
+//   k_png_band<3>  62 VGPRs  85 SGPRs  occupancy 6 waves/SIMD   (what the kernel had before it became a template)
+//   k_png_band<4>  57 VGPRs  73 SGPRs  occupancy 6
+//   k_png_band<0>  62 VGPRs  92 SGPRs  occupancy 6              (the batch: both bodies behind the table lookup)
+//   k_png_layout   44 VGPRs  16 SGPRs  4096 B LDS; k_png_gather 8 VGPRs, 27 SGPRs, no LDS
+// Two workgroups of the band kernel fit a CU's 160 KB of LDS: LDS, not registers, bounds the waves in flight.
 #include "png.hpp"
 
 #include <algorithm>
@@ -52,11 +70,11 @@ namespace s360 {
 
 namespace {
 constexpr int kT = 512;                         // threads per workgroup
-constexpr int kTilePx = 4096;                   // pixels of one row per workgroup iteration
-constexpr int kRawWords = kTilePx * 3 / 4 + 4;  // a tile's bytes + the pixel to its left + alignment slack
+constexpr int kTileBytes = 12288;               // bytes of one row per workgroup iteration: 4096 B,G,R or 3072 B,G,R,A pixels
+constexpr int kRawWords = kTileBytes / 4 + 4;   // a tile's bytes + the pixel to its left + alignment slack
 constexpr int kMaxBits = 15;                    // deflate's longest code
 constexpr int kWaves = kT / 64;
-constexpr int kGroupsPerWave = (kTilePx * 3 / 64 + kWaves - 1) / kWaves;  // 64-byte groups of a tile a wave takes
+constexpr int kGroupsPerWave = (kTileBytes / 64 + kWaves - 1) / kWaves;  // 64-byte groups of a tile a wave takes
 constexpr int kRegionWords = kGroupsPerWave * 64 * kMaxBits / 32 + 4;     // a wave's bits of one tile at the longest code (+ the row's filter-type byte, + slack)
 constexpr int kOutWords = kWaves * kRegionWords;
 constexpr int kSyms = 288;                      // literal/length alphabet, padded (286 symbols exist)
@@ -90,6 +108,14 @@ struct Geo {
   unsigned line;
   unsigned long long band_stride, total_bytes;
 };
+// One image of a batch (device table, png_batch_enqueue): where its pixels lie, its geometry, and where its bands' scratch, its band
+// table and its file image start in the batch's buffers. `band0`: index of its first band among the bands of the whole batch.
+struct BatchImage {
+  const uint8_t* px;
+  Geo G;
+  int channels, band0;
+  unsigned long long scratch_off, meta0, file_off;
+};
 
 // ---- deflate's length codes (RFC 1951, 3.2.5): match length 3..258 -> symbol, extra bits, their value ----
 __device__ inline void length_code(int L, int& sym, int& ebits, int& eval) {
@@ -109,13 +135,14 @@ __device__ inline unsigned rev_bits(unsigned c, int n) {
   return r;
 }
 
-// Row y's pixels [px0, px0 + kTilePx) and the pixel to their left into S.raw (dwords, coalesced); returns the byte offset
+// Row y's pixels [px0, px0 + kTileBytes / C) and the pixel to their left into S.raw (dwords, coalesced); returns the byte offset
 // of pixel px0 in it. `bgr` is 4-byte aligned, `total` its size.
+template <int C>
 __device__ inline int load_tile(Smem& S, const uint8_t* bgr, unsigned long long total, int w, int y, int px0) {
-  const unsigned long long rowb = (unsigned long long)y * w * 3;
-  const unsigned long long a0 = rowb + (unsigned long long)px0 * 3 - (px0 > 0 ? 3 : 0);
-  const int npx = min(kTilePx, w - px0);
-  const unsigned long long a1 = rowb + (unsigned long long)(px0 + npx) * 3;
+  const unsigned long long rowb = (unsigned long long)y * w * C;
+  const unsigned long long a0 = rowb + (unsigned long long)px0 * C - (px0 > 0 ? C : 0);
+  const int npx = min(kTileBytes / C, w - px0);
+  const unsigned long long a1 = rowb + (unsigned long long)(px0 + npx) * C;
   const unsigned long long base = a0 & ~3ull;
   const int nwords = (int)((a1 - base + 3) >> 2);
   // every dword of the thread is requested before the first goes to LDS (as a load-store loop these were up to 13 serialised
@@ -137,7 +164,7 @@ __device__ inline int load_tile(Smem& S, const uint8_t* bgr, unsigned long long 
     if (a + 4 > total) for (int k = 0; k < 4 && a + k < total; ++k) w |= (unsigned)bgr[a + k] << (8 * k);  // (the image's last bytes)
     S.raw[i] = w;
   }
-  return (int)(rowb + (unsigned long long)px0 * 3 - base);
+  return (int)(rowb + (unsigned long long)px0 * C - base);
 }
 
 // ---- a lane per byte -------------------------------------------------------------------------------------------------------
@@ -150,14 +177,15 @@ struct Tok {
   unsigned v;  // the lane's filtered byte
   int r;       // start lane: repeats behind it; any other lane: -1 (nothing to emit)
 };
+template <int C>
 __device__ inline Tok group_tok(const uint8_t* rawb, int off, int px0, int nbytes, int j) {
   const int lane = threadIdx.x & 63;
   const bool valid = j < nbytes;
   const int jj = valid ? j : 0;
-  const int p = jj / 3, c = jj - 3 * p;  // pixel of the tile, channel in PNG order (R,G,B out of B,G,R)
-  const int i = off + 3 * p;
-  const unsigned cur = rawb[i + 2 - c];
-  const unsigned left = (px0 + p == 0) ? 0u : rawb[i - 1 - c];  // Sub: the same channel one pixel to the left, 0 at the row's start
+  const int p = jj / C, c = jj - C * p;  // pixel of the tile, channel in PNG order (R,G,B[,A] out of B,G,R[,A])
+  const int i = off + C * p + (c < 3 ? 2 - c : 3);
+  const unsigned cur = rawb[i];
+  const unsigned left = (px0 + p == 0) ? 0u : rawb[i - C];  // Sub: the same channel one pixel to the left, 0 at the row's start
   Tok t;
   t.v = (cur - left) & 255u;
   // the left neighbour's byte: row_bcast:15 brings lanes 15 / 31 / 47 to the first lanes of the next DPP row, row_shr:1 the rest
@@ -257,18 +285,21 @@ __device__ inline unsigned compact_flush(Smem& S, unsigned* gout, unsigned* gw, 
 }
 
 // filtered byte i of the band starting at row y0, straight from the image (the stored-block path)
+template <int C>
 __device__ inline unsigned filtered_byte(const uint8_t* bgr, const Geo& G, int y0, unsigned i) {
   const unsigned r = i / G.line, k = i - r * G.line;
   if (k == 0) return 1u;
-  const unsigned c = k - 1, p = c / 3, ch = c - 3 * p;
-  const uint8_t* px = bgr + ((unsigned long long)(y0 + r) * G.w + p) * 3;
-  return (unsigned)(px[2 - ch] - (p ? px[-1 - (int)ch] : 0)) & 255u;
+  const unsigned c = k - 1, p = c / C, ch = c - C * p;
+  const uint8_t* px = bgr + ((unsigned long long)(y0 + r) * G.w + p) * C + (ch < 3 ? 2 - ch : 3);
+  return (unsigned)(px[0] - (p ? px[-C] : 0)) & 255u;
 }
 
-__global__ __launch_bounds__(kT) void k_png_band(const uint8_t* __restrict__ bgr, Geo G, uint8_t* __restrict__ scratch,
-                                                  PngBandMeta* __restrict__ meta) {
-  __shared__ Smem S;
-  const int t = threadIdx.x, b = blockIdx.x;
+// Band b of one image of C channels: filter, deflate into the band's scratch, the band's record into meta[b].
+template <int C>
+__device__ inline void band_body(Smem& S, const uint8_t* __restrict__ bgr, const Geo& G, int b, uint8_t* __restrict__ scratch,
+                                 PngBandMeta* __restrict__ meta) {
+  constexpr int kTilePx = kTileBytes / C;  // pixels of one row per workgroup iteration
+  const int t = threadIdx.x;
   const int y0 = b * G.rows_per_band, rows = min(G.rows_per_band, G.h - y0);
   const unsigned n = (unsigned)rows * G.line;
   const bool last = b == G.nbands - 1;
@@ -290,14 +321,14 @@ __global__ __launch_bounds__(kT) void k_png_band(const uint8_t* __restrict__ bgr
     unsigned* H = S.histp[t % kHistCopies];
     for (int r = 0; r < rows; ++r)
       for (int tl = 0; tl < tiles; ++tl) {
-        const int px0 = tl * kTilePx, npx = min(kTilePx, G.w - px0), nbytes = 3 * npx;
-        const int off = load_tile(S, bgr, G.total_bytes, G.w, y0 + r, px0);
+        const int px0 = tl * kTilePx, npx = min(kTilePx, G.w - px0), nbytes = C * npx;
+        const int off = load_tile<C>(S, bgr, G.total_bytes, G.w, y0 + r, px0);
         __syncthreads();
         const int ng = (nbytes + 63) >> 6, per = (ng + kWaves - 1) / kWaves;
-        const unsigned pos0 = (unsigned)r * G.line + 1u + 3u * (unsigned)px0;  // index in the band of the tile's first byte
+        const unsigned pos0 = (unsigned)r * G.line + 1u + (unsigned)C * (unsigned)px0;  // index in the band of the tile's first byte
         for (int g = wv * per; g < min((wv + 1) * per, ng); ++g) {
           const int j = 64 * g + lane;
-          const Tok k = group_tok(rawb, off, px0, nbytes, j);
+          const Tok k = group_tok<C>(rawb, off, px0, nbytes, j);
           if (j < nbytes) {
             sum += k.v;
             wsum += (unsigned long long)(n - (pos0 + (unsigned)j)) * k.v;
@@ -417,7 +448,7 @@ __global__ __launch_bounds__(kT) void k_png_band(const uint8_t* __restrict__ bgr
   }
   if (stored) {
     uint8_t* ob = reinterpret_cast<uint8_t*>(gout);
-    for (unsigned i = t; i < n; i += kT) ob[5u * (i / kStoredMax + 1u) + i] = (uint8_t)filtered_byte(bgr, G, y0, i);
+    for (unsigned i = t; i < n; i += kT) ob[5u * (i / kStoredMax + 1u) + i] = (uint8_t)filtered_byte<C>(bgr, G, y0, i);
     for (unsigned q = t; q < pieces; q += kT) {
       uint8_t* hp = ob + (unsigned long long)q * (kStoredMax + 5u);
       const unsigned len = min(kStoredMax, n - q * kStoredMax);
@@ -458,8 +489,8 @@ __global__ __launch_bounds__(kT) void k_png_band(const uint8_t* __restrict__ bgr
   unsigned pend = compact_flush(S, gout, &gw, 0u, &carry);
   for (int r = 0; r < rows; ++r)
     for (int tl = 0; tl < tiles; ++tl) {
-      const int px0 = tl * kTilePx, npx = min(kTilePx, G.w - px0), nbytes = 3 * npx;
-      const int off = load_tile(S, bgr, G.total_bytes, G.w, y0 + r, px0);
+      const int px0 = tl * kTilePx, npx = min(kTilePx, G.w - px0), nbytes = C * npx;
+      const int off = load_tile<C>(S, bgr, G.total_bytes, G.w, y0 + r, px0);
       __syncthreads();
       const int ng = (nbytes + 63) >> 6, per = (ng + kWaves - 1) / kWaves;
       const int g0 = wv * per, g1 = min(g0 + per, ng);
@@ -472,7 +503,7 @@ __global__ __launch_bounds__(kT) void k_png_band(const uint8_t* __restrict__ bgr
         at = leadc >> 16;
       }
       for (int g = g0; g < g1; ++g) {
-        const Tok k = group_tok(rawb, off, px0, nbytes, 64 * g + lane);
+        const Tok k = group_tok<C>(rawb, off, px0, nbytes, 64 * g + lane);
         const unsigned bits = tok_bits(S, k);
         const unsigned incl = wave_scan(bits);
         if (k.r >= 0) {  // this lane's tokens as one value: the literal, then the match or the literal again
@@ -518,9 +549,33 @@ __global__ __launch_bounds__(kT) void k_png_band(const uint8_t* __restrict__ bgr
   if (t == 0 && pend) gout[gw] = carry;  // (the last band's final bits; the band's reserve covers the dword)
 }
 
-// where every band's IDAT chunk starts in the file: prefix sum of 12 + bytes behind the preamble (one workgroup)
-__global__ __launch_bounds__(kT) void k_png_layout(PngBandMeta* __restrict__ meta, int nbands) {
+// C = 3 / 4: one image, a workgroup per band. C = 0: the bands of a batch of images — band_img[blockIdx.x] names the band's image in
+// `imgs`, whose record gives pixels, geometry, channel count and the image's places in the batch's scratch and band tables. Every
+// band is a workgroup of its own and runs for its own rows only: a small image's band leaves its CU as soon as it is done.
+template <int C>
+__global__ __launch_bounds__(kT) void k_png_band(const uint8_t* __restrict__ bgr, Geo G, uint8_t* __restrict__ scratch,
+                                                  PngBandMeta* __restrict__ meta, const BatchImage* __restrict__ imgs,
+                                                  const int* __restrict__ band_img) {
+  __shared__ Smem S;
+  if constexpr (C == 0) {
+    const BatchImage& I = imgs[band_img[blockIdx.x]];
+    const Geo Gi = I.G;
+    const int b = (int)blockIdx.x - I.band0;
+    if (I.channels == 4) band_body<4>(S, I.px, Gi, b, scratch + I.scratch_off, meta + I.meta0);
+    else band_body<3>(S, I.px, Gi, b, scratch + I.scratch_off, meta + I.meta0);
+  } else {
+    band_body<C>(S, bgr, G, (int)blockIdx.x, scratch, meta);
+  }
+}
+
+// where every band's IDAT chunk starts in its file: prefix sum of 12 + bytes behind the preamble. One workgroup per image (the
+// sum is segmented: every image of a batch has a band table and a file of its own); imgs == nullptr: the one image of meta / nbands.
+__global__ __launch_bounds__(kT) void k_png_layout(PngBandMeta* __restrict__ meta, int nbands, const BatchImage* __restrict__ imgs) {
   __shared__ unsigned long long part[kT];
+  if (imgs) {
+    meta += imgs[blockIdx.x].meta0;
+    nbands = imgs[blockIdx.x].G.nbands;
+  }
   const int t = threadIdx.x, per = (nbands + kT - 1) / kT;
   const int i0 = min(t * per, nbands), i1 = min(i0 + per, nbands);
   unsigned long long s = 0;
@@ -539,9 +594,20 @@ __global__ __launch_bounds__(kT) void k_png_layout(PngBandMeta* __restrict__ met
 }
 
 // band b to its place in the file: length (big-endian) + "IDAT" + the bytes; the chunk's CRC stays for the host
+// (a batch: band_img / imgs as in k_png_band, `file` the batch's file buffer)
 __global__ __launch_bounds__(kT) void k_png_gather(const uint8_t* __restrict__ scratch, unsigned long long band_stride,
-                                                    const PngBandMeta* __restrict__ meta, uint8_t* __restrict__ file) {
-  const int t = threadIdx.x, b = blockIdx.x;
+                                                    const PngBandMeta* __restrict__ meta, uint8_t* __restrict__ file,
+                                                    const BatchImage* __restrict__ imgs, const int* __restrict__ band_img) {
+  const int t = threadIdx.x;
+  int b = blockIdx.x;
+  if (imgs) {
+    const BatchImage& I = imgs[band_img[b]];
+    b -= I.band0;
+    scratch += I.scratch_off;
+    band_stride = I.G.band_stride;
+    meta += I.meta0;
+    file += I.file_off;
+  }
   const unsigned bytes = meta[b].bytes;
   uint8_t* dst = file + meta[b].file_off;
   if (t < 8) {
@@ -564,12 +630,14 @@ __global__ __launch_bounds__(kT) void k_png_gather(const uint8_t* __restrict__ s
 inline size_t cdivz(size_t a, size_t b) { return (a + b - 1) / b; }
 }  // namespace
 
-PngPlan PngPlan::make(int w, int h) {
+PngPlan PngPlan::make(int w, int h, int channels) {
   if (w < 1 || h < 1 || w > 65535 || h > 65535) throw Error(S360_ERR_INVALID_ARG, "png: unsupported image size");
+  if (channels != 3 && channels != 4) throw Error(S360_ERR_INVALID_ARG, "png: channels must be 3 (B,G,R) or 4 (B,G,R,A)");
   PngPlan p;
   p.w = w;
   p.h = h;
-  p.line = 1 + 3 * (size_t)w;
+  p.channels = channels;
+  p.line = 1 + (size_t)channels * (size_t)w;
   // ~192 KB of scanlines per band, at least ~64 bands in a tall image (small frames still spread over the chip)
   const size_t by_size = std::max<size_t>(1, ((size_t)192 << 10) / p.line), by_count = cdivz((size_t)h, 64);
   p.rows_per_band = (int)std::max<size_t>(1, std::min(std::min(by_size, by_count), (size_t)h));
@@ -582,21 +650,83 @@ PngPlan PngPlan::make(int w, int h) {
   return p;
 }
 
-void png_encode_enqueue(hipStream_t st, const uint8_t* bgr, const PngPlan& P, DevBuf& scratch, DevBuf& meta, uint8_t* file) {
-  if (reinterpret_cast<uintptr_t>(bgr) & 3) throw Error(S360_ERR_INVALID_ARG, "png: image not 4-byte aligned");
-  scratch.ensure((size_t)P.nbands * P.band_stride);
-  meta.ensure(((size_t)P.nbands + 1) * sizeof(PngBandMeta));
+namespace {
+Geo geo_of(const PngPlan& P) {
   Geo G;
   G.w = P.w; G.h = P.h; G.rows_per_band = P.rows_per_band; G.nbands = P.nbands;
   G.line = (unsigned)P.line;
   G.band_stride = P.band_stride;
-  G.total_bytes = (unsigned long long)P.w * P.h * 3;
-  hipLaunchKernelGGL(k_png_band, dim3(P.nbands), dim3(kT), 0, st, bgr, G, scratch.as<uint8_t>(), meta.as<PngBandMeta>());
-  hipLaunchKernelGGL(k_png_layout, dim3(1), dim3(kT), 0, st, meta.as<PngBandMeta>(), P.nbands);
+  G.total_bytes = (unsigned long long)P.w * P.h * P.channels;
+  return G;
+}
+}  // namespace
+
+void png_encode_enqueue(hipStream_t st, const uint8_t* bgr, const PngPlan& P, DevBuf& scratch, DevBuf& meta, uint8_t* file) {
+  if (reinterpret_cast<uintptr_t>(bgr) & 3) throw Error(S360_ERR_INVALID_ARG, "png: image not 4-byte aligned");
+  scratch.ensure((size_t)P.nbands * P.band_stride);
+  meta.ensure(((size_t)P.nbands + 1) * sizeof(PngBandMeta));
+  const Geo G = geo_of(P);
+  const BatchImage* none = nullptr;
+  const int* nomap = nullptr;
+  if (P.channels == 4)
+    hipLaunchKernelGGL(k_png_band<4>, dim3(P.nbands), dim3(kT), 0, st, bgr, G, scratch.as<uint8_t>(), meta.as<PngBandMeta>(), none, nomap);
+  else
+    hipLaunchKernelGGL(k_png_band<3>, dim3(P.nbands), dim3(kT), 0, st, bgr, G, scratch.as<uint8_t>(), meta.as<PngBandMeta>(), none, nomap);
+  hipLaunchKernelGGL(k_png_layout, dim3(1), dim3(kT), 0, st, meta.as<PngBandMeta>(), P.nbands, none);
   hipLaunchKernelGGL(k_png_gather, dim3(P.nbands), dim3(kT), 0, st, scratch.as<uint8_t>(), (unsigned long long)P.band_stride,
-                     meta.as<PngBandMeta>(), file);
+                     meta.as<PngBandMeta>(), file, none, nomap);
   S360_HIP(hipGetLastError());
 }
+
+PngBatchPlan PngBatchPlan::make(const std::vector<PngPlan>& plans) {
+  PngBatchPlan B;
+  B.img = plans;
+  for (const PngPlan& P : plans) {
+    B.band0.push_back(B.nbands);
+    B.scratch_off.push_back(B.scratch_bytes);
+    B.meta0.push_back(B.meta_records);
+    B.file_off.push_back(B.file_bytes);
+    B.nbands += P.nbands;
+    B.scratch_bytes += (size_t)P.nbands * P.band_stride;            // (band_stride is a multiple of 16)
+    B.meta_records += (size_t)P.nbands + 1;
+    B.file_bytes += (P.file_bound + 15) & ~(size_t)15;
+  }
+  return B;
+}
+
+void png_batch_enqueue(hipStream_t st, const uint8_t* const* px, const PngBatchPlan& B, DevBuf& table, void* table_host, DevBuf& scratch,
+                       DevBuf& meta, DevBuf& files) {
+  const size_t n = B.img.size();
+  if (!n) return;
+  const size_t tbytes = PngBatchPlan::table_bytes(n, (size_t)B.nbands);
+  table.ensure(tbytes);
+  scratch.ensure(B.scratch_bytes);
+  meta.ensure(B.meta_records * sizeof(PngBandMeta));
+  files.ensure(B.file_bytes);
+  BatchImage* I = static_cast<BatchImage*>(table_host);
+  int* map = reinterpret_cast<int*>(I + n);
+  for (size_t i = 0; i < n; ++i) {
+    if (reinterpret_cast<uintptr_t>(px[i]) & 3) throw Error(S360_ERR_INVALID_ARG, "png: image not 4-byte aligned");
+    I[i].px = px[i];
+    I[i].G = geo_of(B.img[i]);
+    I[i].channels = B.img[i].channels;
+    I[i].band0 = B.band0[i];
+    I[i].scratch_off = B.scratch_off[i];
+    I[i].meta0 = B.meta0[i];
+    I[i].file_off = B.file_off[i];
+    for (int b = 0; b < B.img[i].nbands; ++b) map[B.band0[i] + b] = (int)i;
+  }
+  S360_HIP(hipMemcpyAsync(table.p, table_host, tbytes, hipMemcpyHostToDevice, st));
+  const BatchImage* dI = table.as<BatchImage>();
+  const int* dmap = reinterpret_cast<const int*>(dI + n);
+  const uint8_t* nopx = nullptr;
+  hipLaunchKernelGGL(k_png_band<0>, dim3(B.nbands), dim3(kT), 0, st, nopx, Geo{}, scratch.as<uint8_t>(), meta.as<PngBandMeta>(), dI, dmap);
+  hipLaunchKernelGGL(k_png_layout, dim3((unsigned)n), dim3(kT), 0, st, meta.as<PngBandMeta>(), 0, dI);
+  hipLaunchKernelGGL(k_png_gather, dim3(B.nbands), dim3(kT), 0, st, scratch.as<uint8_t>(), 0ull, meta.as<PngBandMeta>(), files.as<uint8_t>(), dI,
+                     dmap);
+  S360_HIP(hipGetLastError());
+}
+size_t PngBatchPlan::table_bytes(size_t n, size_t nbands) { return n * sizeof(BatchImage) + nbands * sizeof(int); }
 
 // ---- host side: CRC-32 (the PNG / zlib polynomial 0xEDB88320, eight tables, eight bytes per step) ----
 namespace {
@@ -653,7 +783,7 @@ size_t png_finish_host(uint8_t* file, size_t cap, const PngPlan& P, const PngBan
   uint8_t ihdr[13];
   be32(ihdr, (uint32_t)P.w);
   be32(ihdr + 4, (uint32_t)P.h);
-  ihdr[8] = 8; ihdr[9] = 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;  // 8-bit RGB, deflate, adaptive filtering, not interlaced
+  ihdr[8] = 8; ihdr[9] = P.channels == 4 ? 6 : 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;  // 8-bit RGB / RGBA, deflate, adaptive filtering, not interlaced
   at += put_chunk(file + at, "IHDR", ihdr, 13);
   uint8_t br[4];
   be32(br, (uint32_t)P.rows_per_band);

@@ -431,14 +431,59 @@ class Context:
         return out[:n.value]
 
     def encode_png(self, bgr):
-        """Operator form: an (h, w, 3) uint8 B,G,R image -> the bytes of a PNG file (8-bit RGB), encoded on the device."""
+        """Operator form: an (h, w, 3) uint8 B,G,R image -> the bytes of a PNG file (8-bit RGB), or an (h, w, 4) B,G,R,A image ->
+        an 8-bit RGBA file (alpha kept), encoded on the device."""
         bgr = np.ascontiguousarray(bgr, np.uint8)
         h, w = bgr.shape[:2]
+        if bgr.shape == (h, w, 4):
+            return self.encode_png_c(bgr)
         assert bgr.shape == (h, w, 3)
         out = np.empty(int(lib().s360_png_bound(w, h)), np.uint8)
         n = C.c_size_t(0)
         self._ck(lib().s360_encode_png(self.h, _p(bgr), w, h, _p(out), C.c_size_t(out.size), C.byref(n)))
         return out[:n.value].tobytes()
+
+    def encode_png_c(self, px, channels=None):
+        """s360_encode_png_c: the same encoder with the channel count spelled out (3 or 4; the default is the array's)."""
+        px = np.ascontiguousarray(px, np.uint8)
+        h, w = px.shape[:2]
+        ch = int(px.shape[2] if channels is None else channels)
+        cap = int(lib().s360_png_bound_c(w, h, ch))
+        out = np.empty(max(cap, 1), np.uint8)
+        n = C.c_size_t(0)
+        self._ck(lib().s360_encode_png_c(self.h, _p(px), w, h, ch, _p(out), C.c_size_t(cap), C.byref(n)))
+        return out[:n.value].tobytes()
+
+    def encode_png_batch(self, images):
+        """s360_encode_png_batch: a list of (h, w, 3) / (h, w, 4) uint8 images of any sizes -> the list of their PNG files, encoded
+        by one launch sequence on the device."""
+        imgs = [np.ascontiguousarray(a, np.uint8) for a in images]
+        k = len(imgs)
+        assert k > 0 and all(a.ndim == 3 and a.shape[2] in (3, 4) for a in imgs)
+        outs = [np.empty(int(lib().s360_png_bound_c(a.shape[1], a.shape[0], a.shape[2])), np.uint8) for a in imgs]
+        ints = lambda v: (C.c_int * k)(*v)  # noqa: E731
+        n = (C.c_size_t * k)()
+        self._ck(lib().s360_encode_png_batch(
+            self.h, k, (C.c_void_p * k)(*[a.ctypes.data for a in imgs]), ints([a.shape[1] for a in imgs]), ints([a.shape[0] for a in imgs]),
+            ints([a.shape[2] for a in imgs]), (C.c_void_p * k)(*[o.ctypes.data for o in outs]), (C.c_size_t * k)(*[o.size for o in outs]), n))
+        return [o[:n[i]].tobytes() for i, o in enumerate(outs)]
+
+    def encode_state_pngs(self, names_idx):
+        """s360_frame_encode_state_pngs: enqueues the batched encode of the named 4-channel intermediates of the selected slot's
+        latest frame — a list of (name, idx) with the names of get_u8 — behind that frame's kernels. Waits for nothing; the files
+        are fetched with download_state_png(i), i the position in this list."""
+        k = len(names_idx)
+        names = (C.c_char_p * k)(*[n.encode() for n, _ in names_idx])
+        self._ck(lib().s360_frame_encode_state_pngs(self.h, k, names, (C.c_int * k)(*[int(i) for _, i in names_idx])))
+
+    def download_state_png(self, i, out=None):
+        """File i of the last encode_state_pngs call: a view of its bytes in `out` (a uint8 buffer; default: one of the file's bound)."""
+        if out is None:
+            out = np.empty(max(int(lib().s360_frame_state_png_bound(self.h, int(i))), 1), np.uint8)
+        assert out.dtype == np.uint8 and out.ndim == 1 and out.flags["C_CONTIGUOUS"]
+        n = C.c_size_t(0)
+        self._ck(lib().s360_frame_download_state_png(self.h, int(i), _p(out), C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value]
 
     def uploads_complete(self):
         """Blocks until every upload enqueued so far has left its host buffer (needed for buffers from pinned_empty only)."""
