@@ -65,6 +65,12 @@ struct Flags {
          // batched launch sequence per context (s360_frame_encode_state_pngs) — and this program only writes the files' bytes;
          // off: their pixels come back raw and host threads deflate them (png_io.hpp). Same pixels in the files either way.
          {"device_state_png", "false"},
+         // --device_state_read (default off; S360_DEVICE_STATE_READ=1 in the environment switches it on too): the state IMAGES of
+         // --prev_frame_data_dir are read as bytes and inflated and unfiltered on the GPU that takes them — one batched decode per
+         // context (s360_frame_set_prev_images_png), the flows through s360_frame_set_prev_flow — instead of host threads
+         // inflating them (png_io.hpp) and their pixels being uploaded. A file the device decoder does not take (cv::imwrite's,
+         // the reference program's) takes the host path for its pair or unit. Same state on the device either way.
+         {"device_state_read", "false"},
          // --num_gpus G: the 14 side pairs of the frame sharded over G GPUs, one RCCL strip gather
          {"num_gpus", "1"},
          // --num_frames N: frames frame_number .. +N-1 as ONE stream in this process (temporal state stays on the
@@ -90,7 +96,7 @@ struct Flags {
   }
   static bool is_bool(const std::string& k) {
     static const char* b[] = {"save_debug_images", "enable_top", "enable_bottom", "enable_pole_removal", "logtostderr",
-                              "alsologtostderr", "write_state", "soft_isp", "device_png", "device_state_png"};
+                              "alsologtostderr", "write_state", "soft_isp", "device_png", "device_state_png", "device_state_read"};
     for (auto s : b)
       if (k == s) return true;
     return false;
@@ -424,7 +430,10 @@ class ItemPool {
 // previous frame's state from files (TRSP:215-235, 421-436), each pair to the GPU that renders it. The 68 files of an 8K frame
 // (1.2 GB of flows, 0.9 GB of images behind their PNG coding) are read and decoded by a pool of threads — the reference reads
 // them inside its per-pair / per-unit threads, TRSP:215-235 —, then handed to the library in order.
+void load_prev_state_device(const Job& J, const std::string& prev);
+bool device_state_read(const Flags& F);
 void load_prev_state(const Job& J, const std::string& prev) {
+  if (device_state_read(J.F)) return load_prev_state_device(J, prev);
   const s360_geometry& g = J.g;
   const std::string outData = J.F.s("output_data_dir");
   const std::string flowPrevDir = outData + "/flow/" + prev, imgPrevDir = outData + "/debug/" + prev + "/flow_images/";
@@ -497,6 +506,212 @@ void load_prev_state(const Job& J, const std::string& prev) {
     ck(s360_frame_set_prev_pole(J.owner_ctx(u), u, us.pf.data(), us.S.px.data(), us.Fi.px.data()), J.owner_ctx(u));  // a unit's state lives where it runs
     us = UnitState();
   }
+}
+
+// --device_state_read: the same state, its images decoded on the device. The image files are read as bytes (a pool of threads);
+// those of a pair / pole unit / the pole removal whose files the device decoder takes go in ONE s360_frame_set_prev_images_png per
+// context — a pair on the rank of its partition, a pole unit on its owner, the pole-removal images on the bottom GPU — while the
+// pool reads the 1.2 GB of flow files (S360_STATE_READ_ORDER=batch, developer switch: the decode waits for them instead); the
+// flows follow through s360_frame_set_prev_flow. A pair or unit with a file the decoder does not take goes the way of
+// load_prev_state. A file the device finds damaged dies with the host reader's message.
+struct PrevTimes { double files = 0, decode = 0, flows = 0; int onDevice = 0, onHost = 0; bool used = false; };  // seconds of the loading thread; images
+PrevTimes g_prevTimes;
+bool device_state_read(const Flags& F) {
+  const char* e = std::getenv("S360_DEVICE_STATE_READ");
+  return F.b("device_state_read") || (e && !std::strcmp(e, "1"));
+}
+std::vector<uint8_t> read_bytes(const std::string& path) {
+  std::vector<uint8_t> b;
+  FILE* f = std::fopen(path.c_str(), "rb");
+  if (!f) die("failed to load image: " + path);
+  if (std::fseek(f, 0, SEEK_END) == 0) {
+    const long sz = std::ftell(f);
+    std::rewind(f);
+    if (sz > 0) {
+      b.resize((size_t)sz);
+      b.resize(std::fread(b.data(), 1, (size_t)sz, f));
+    }
+  }
+  std::fclose(f);
+  return b;
+}
+void load_prev_state_device(const Job& J, const std::string& prev) {
+  const s360_geometry& g = J.g;
+  const std::string outData = J.F.s("output_data_dir");
+  const std::string flowPrevDir = outData + "/flow/" + prev, imgPrevDir = outData + "/debug/" + prev + "/flow_images/";
+  const char* ord = std::getenv("S360_STATE_READ_ORDER");
+  const bool overlap = !(ord && !std::strcmp(ord, "batch"));
+  const bool pr = J.prm.enable_pole_removal;
+  // groups: pairs 0..P-1, pole units P..P+3, pole removal P+4; every group's image files and flow files
+  struct Img { std::string path, name; int idx = 0, group = 0; std::vector<uint8_t> bytes; int whc[3] = {0, 0, 0}; bool ours = false; };
+  struct Flow { std::string path, name; int idx = 0, group = 0, w = 0, h = 0; std::vector<float> px; };
+  std::vector<Img> imgs;
+  std::vector<Flow> flows;
+  auto add_img = [&](int group, const std::string& file, const char* name, int idx) {
+    Img m; m.path = imgPrevDir + "/" + file; m.name = name; m.idx = idx; m.group = group;
+    imgs.push_back(std::move(m));
+  };
+  auto add_flow = [&](int group, const std::string& file, const char* name, int idx, int w, int h) {
+    Flow f; f.path = flowPrevDir + "/" + file; f.name = name; f.idx = idx; f.group = group; f.w = w; f.h = h;
+    flows.push_back(std::move(f));
+  };
+  bool unitOn[4];
+  for (int u = 0; u < 4; ++u) {  // (the largest files first)
+    unitOn[u] = !((u < 2 && !J.prm.enable_top) || (u >= 2 && !J.prm.enable_bottom));
+    if (!unitOn[u]) continue;
+    add_img(J.P + u, std::string("extendedSideSpherical_") + kEyeNames[u] + ".png", "extended_side", u);
+    add_img(J.P + u, std::string("extendedFisheyeSpherical_") + kEyeNames[u] + ".png", "extended_fisheye", u);
+    add_flow(J.P + u, std::string("flow_") + kEyeNames[u] + ".bin", "flow_pole", u, J.extW, u < 2 ? g.top_rows : g.bottom_rows);
+  }
+  if (pr) {
+    add_img(J.P + 4, "bottomImage.png", "bottom_image", 0);
+    add_img(J.P + 4, "bottomImage2.png", "bottom_image2", 0);
+    add_flow(J.P + 4, "flow_bottom_secondary.bin", "flow_bottom_secondary", 0, 0, 0);
+  }
+  for (int i = 0; i < J.P; ++i) {
+    add_img(i, "overlap_" + std::to_string(i) + "_L.png", "overlap_l", i);
+    add_img(i, "overlap_" + std::to_string(i) + "_R.png", "overlap_r", i);
+    add_flow(i, "flowLtoR_" + std::to_string(i) + ".bin", "flow_l_to_r", i, g.overlap_image_width, g.cam_image_height);
+    add_flow(i, "flowRtoL_" + std::to_string(i) + ".bin", "flow_r_to_l", i, g.overlap_image_width, g.cam_image_height);
+  }
+  const double t0 = now_sec();
+  parallel_items((int)imgs.size(), state_workers(), [&](int k) {
+    Img& m = imgs[k];
+    m.bytes = read_bytes(m.path);
+    int rows = 0;
+    m.ours = s360_png_decodable(m.bytes.data(), m.bytes.size(), m.whc, &rows) == S360_OK;
+  });
+  auto read_flow = [&](int k) {
+    Flow& f = flows[k];
+    if (f.w == 0) {  // flow_bottom_secondary: its size is the file's (PoleRemoval.cpp:95-110)
+      if (s360_read_flow_from_file(f.path.c_str(), nullptr, &f.w, &f.h, 0) < 0)
+        die(std::string("bad previous flow file: flow_bottom_secondary.bin: ") + s360_last_error(nullptr));
+      f.px.resize((size_t)f.w * f.h * 2);
+      if (s360_read_flow_from_file(f.path.c_str(), f.px.data(), &f.w, &f.h, f.px.size()) < 0)
+        die(std::string("bad previous flow file: flow_bottom_secondary.bin: ") + s360_last_error(nullptr));
+      return;
+    }
+    f.px.resize((size_t)f.w * f.h * 2);
+    int w = 0, h = 0;
+    if (s360_read_flow_from_file(f.path.c_str(), f.px.data(), &w, &h, f.px.size()) < 0 || w != f.w || h != f.h) {
+      if (f.group < J.P) die("bad previous flow file for pair " + std::to_string(f.idx) + ": " + s360_last_error(nullptr));
+      die(std::string("bad previous pole flow file: ") + kEyeNames[f.idx]);
+    }
+  };
+  const double t1 = now_sec();
+  std::unique_ptr<ItemPool> flowPool;
+  if (overlap) flowPool.reset(new ItemPool((int)flows.size(), state_workers(), read_flow));
+  else parallel_items((int)flows.size(), state_workers(), read_flow);
+  const double t2 = now_sec();
+  // which groups go to the device decoder: every image of the group is a file it takes, of the size the state has
+  std::vector<char> dev((size_t)J.P + 5, 1);
+  for (const Img& m : imgs) {
+    if (!m.ours) { dev[(size_t)m.group] = 0; continue; }
+    if (m.group < J.P) {
+      if (m.whc[2] != 4 || m.whc[0] != g.overlap_image_width || m.whc[1] != g.cam_image_height) die("previous overlap images have the wrong size/channels");
+    } else if (m.group < J.P + 4) {
+      const int rows = m.idx < 2 ? g.top_rows : g.bottom_rows;
+      if (m.whc[2] != 4 || m.whc[0] != J.extW || m.whc[1] != rows) die("previous extended pole images have the wrong size/channels");
+    }
+  }
+  if (pr && dev[(size_t)J.P + 4])  // PoleRemoval.cpp:95-110: the two images have the size of the flow between them
+    for (size_t k = 0; k < flows.size(); ++k)
+      if (flows[k].group == J.P + 4) {
+        if (flowPool) flowPool->wait((int)k);
+        for (const Img& m : imgs)
+          if (m.group == J.P + 4 && (m.whc[2] != 4 || m.whc[0] != flows[k].w || m.whc[1] != flows[k].h))
+            die("previous bottomImage / bottomImage2 have the wrong size/channels");
+      }
+  auto ctx_of = [&](int group) -> s360_ctx* {
+    if (group < J.P) {
+      for (size_t r = 0; r < J.ctx.size(); ++r)
+        if (group >= J.bounds[r] && group < J.bounds[r + 1]) return J.ctx[r];
+      return J.ctx[0];
+    }
+    return group < J.P + 4 ? J.owner_ctx(group - J.P) : J.ctx[J.bottom_gpu()];
+  };
+  for (size_t r = 0; r < J.ctx.size(); ++r) ck(s360_frame_set_partition(J.ctx[r], J.bounds[r], J.bounds[r + 1]), J.ctx[r]);
+  for (s360_ctx* c : J.ctx) {  // one batched decode per context
+    std::vector<const char*> names;
+    std::vector<int> idx;
+    std::vector<const uint8_t*> files;
+    std::vector<size_t> bytes;
+    std::vector<const Img*> which;
+    for (const Img& m : imgs)
+      if (dev[(size_t)m.group] && ctx_of(m.group) == c) {
+        names.push_back(m.name.c_str()); idx.push_back(m.idx); files.push_back(m.bytes.data()); bytes.push_back(m.bytes.size());
+        which.push_back(&m);
+      }
+    if (names.empty()) continue;
+    if (s360_frame_set_prev_images_png(c, (int)names.size(), names.data(), idx.data(), files.data(), bytes.data()) != S360_OK) {
+      const std::string e = s360_last_error(c);
+      int image = -1, reason = S360_PNG_DECODE_FAILURE_NONE;
+      (void)s360_png_decode_failure(c, &image, &reason);
+      if (reason == S360_PNG_DECODE_FAILURE_DAMAGED && image >= 0 && (size_t)image < which.size())
+        die("corrupt PNG data: " + which[(size_t)image]->path);  // (the host reader's message)
+      die(e);
+    }
+  }
+  const double t3 = now_sec();
+  // the flows; and the groups that take the host path: their images through png_io.hpp, handed in by the calls of load_prev_state
+  auto flow_of = [&](int group, const char* name) -> Flow& {
+    for (size_t k = 0; k < flows.size(); ++k)
+      if (flows[k].group == group && flows[k].name == name) {
+        if (flowPool) flowPool->wait((int)k);
+        return flows[k];
+      }
+    die("internal: no such flow");
+    return flows[0];
+  };
+  auto host_decode = [&](int group, const char* name) -> pngio::Image {  // (the file's bytes are in memory already)
+    for (const Img& m : imgs)
+      if (m.group == group && m.name == name) {
+        try {
+          return jpegio::decode_any(m.bytes, m.path, true);
+        } catch (const std::exception& e) {
+          die(e.what());
+        }
+      }
+    die("internal: no such image");
+  };
+  for (int grp = 0; grp < J.P + 5; ++grp) {
+    if (grp >= J.P && grp < J.P + 4 && !unitOn[grp - J.P]) continue;
+    if (grp == J.P + 4 && !pr) continue;
+    s360_ctx* c = ctx_of(grp);
+    if (dev[(size_t)grp]) {
+      for (size_t k = 0; k < flows.size(); ++k)
+        if (flows[k].group == grp) {
+          if (flowPool) flowPool->wait((int)k);
+          ck(s360_frame_set_prev_flow(c, flows[k].name.c_str(), flows[k].idx, flows[k].px.data()), c);
+          std::vector<float>().swap(flows[k].px);
+        }
+      continue;
+    }
+    if (grp < J.P) {
+      const pngio::Image L = host_decode(grp, "overlap_l"), R = host_decode(grp, "overlap_r");
+      if (L.c != 4 || R.c != 4 || L.w != g.overlap_image_width || L.h != g.cam_image_height || R.w != L.w || R.h != L.h)
+        die("previous overlap images have the wrong size/channels");
+      ck(s360_frame_set_prev_side(c, grp, flow_of(grp, "flow_l_to_r").px.data(), flow_of(grp, "flow_r_to_l").px.data(), L.px.data(), R.px.data()), c);
+    } else if (grp < J.P + 4) {
+      const int u = grp - J.P, rows = u < 2 ? g.top_rows : g.bottom_rows;
+      const pngio::Image S = host_decode(grp, "extended_side"), Fi = host_decode(grp, "extended_fisheye");
+      if (S.c != 4 || Fi.c != 4 || S.w != J.extW || S.h != rows || Fi.w != J.extW || Fi.h != rows)
+        die("previous extended pole images have the wrong size/channels");
+      ck(s360_frame_set_prev_pole(c, u, flow_of(grp, "flow_pole").px.data(), S.px.data(), Fi.px.data()), c);
+    } else {
+      Flow& f = flow_of(grp, "flow_bottom_secondary");
+      const pngio::Image b1 = host_decode(grp, "bottom_image"), b2 = host_decode(grp, "bottom_image2");
+      if (b1.c != 4 || b2.c != 4 || b1.w != f.w || b1.h != f.h || b2.w != f.w || b2.h != f.h)
+        die("previous bottomImage / bottomImage2 have the wrong size/channels");
+      ck(s360_frame_set_prev_pole_removal(c, f.px.data(), b1.px.data(), b2.px.data(), f.w, f.h), c);
+    }
+  }
+  const double t4 = now_sec();
+  g_prevTimes.used = true;
+  for (const Img& m : imgs) ++(dev[(size_t)m.group] ? g_prevTimes.onDevice : g_prevTimes.onHost);
+  g_prevTimes.files += (t1 - t0) + (overlap ? 0.0 : t2 - t1);
+  g_prevTimes.decode += t3 - t2;
+  g_prevTimes.flows += t4 - t3;
 }
 
 // Enqueue one frame. One GPU: the whole frame on its stream. G GPUs (TRSP:320-385): every GPU renders its
@@ -954,7 +1169,11 @@ static int run_job(const Flags& flags) {
     std::fprintf(stderr, "--- Runtime breakdown (sec) ---\n");
     std::fprintf(stderr, "load + decode + upload:  %.3f  (flags + rig %.3f, HIP start-up + context %.3f beside the PNG decodes, waiting for them %.3f, upload %.3f)\n",
                  loadTime - startTime, rigTime - startTime, ctxTime - rigTime, decodeTime - ctxTime, loadTime - decodeTime);
-    std::fprintf(stderr, "previous-frame state:    %.3f\n", renderStart - loadTime);
+    if (g_prevTimes.used)
+      std::fprintf(stderr, "previous-frame state:    %.3f  (reading the image files %.3f, device decode %.3f, flows %.3f; %d images decoded on the device, %d on the host)\n",
+                   renderStart - loadTime, g_prevTimes.files, g_prevTimes.decode, g_prevTimes.flows, g_prevTimes.onDevice, g_prevTimes.onHost);
+    else
+      std::fprintf(stderr, "previous-frame state:    %.3f\n", renderStart - loadTime);
     if (numFrames == 1) {
       std::fprintf(stderr, "GPU render + download:   %.3f  (%d GPU%s)\n", renderEnd - renderStart, G, G > 1 ? "s, RCCL strip gather" : "");
       std::fprintf(stderr, "state files:             %.3f  (beside the equirect's PNG encoder)\n", stateEnd - renderEnd);

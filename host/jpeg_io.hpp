@@ -479,4 +479,12 @@ inline void read_any_into(const std::string& path, bool keep_alpha, pngio::Image
   else pngio::read_into(path, keep_alpha, im);
 }
 
+// ... and for a file that is already in memory
+inline pngio::Image decode_any(const std::vector<uint8_t>& file, const std::string& path, bool keep_alpha) {
+  if (file.size() >= 2 && file[0] == 0xFF && file[1] == 0xD8) return Reader(file, path).decode();
+  pngio::Image im;
+  pngio::decode_into(file, path, keep_alpha, im);
+  return im;
+}
+
 }  // namespace jpegio

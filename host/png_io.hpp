@@ -99,6 +99,7 @@ inline void unfilter_paeth_px(uint8_t* cur, const uint8_t* prev, size_t stride) 
 // `im` is overwritten; its pixel buffer is reused when it is large enough (a stream hands the previous frames' images
 // back to its decoders: 17 x 12.6 MB mapped, page-faulted and unmapped per frame cost more than the decoding).
 inline int g_read_threads = 0;  // threads of the parallel band reader (0: by the image's size, up to 8; < 0: sequential reader only)
+inline void decode_into(const std::vector<uint8_t>& file, const std::string& path, bool keep_alpha, Image& im);
 inline void read_into(const std::string& path, bool keep_alpha, Image& im) {
   FILE* f = std::fopen(path.c_str(), "rb");
   if (!f) throw std::runtime_error("failed to load image: " + path);
@@ -115,6 +116,10 @@ inline void read_into(const std::string& path, bool keep_alpha, Image& im) {
   size_t n;
   while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) file.insert(file.end(), buf, buf + n);  // (a source that cannot seek, or grew)
   std::fclose(f);
+  decode_into(file, path, keep_alpha, im);
+}
+// ... the same for a file that is already in memory (`path` names it in the messages)
+inline void decode_into(const std::vector<uint8_t>& file, const std::string& path, bool keep_alpha, Image& im) {
   static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
   if (file.size() < 8 || std::memcmp(file.data(), sig, 8) != 0) throw std::runtime_error("not a PNG file: " + path);
   size_t pos = 8;
@@ -188,7 +193,7 @@ inline void read_into(const std::string& path, bool keep_alpha, Image& im) {
         z_stream z2;
         std::memset(&z2, 0, sizeof z2);
         if (inflateInit2(&z2, -15) != Z_OK) { bad = true; return; }
-        z2.next_in = &file[idat_chunks[bi + 1].first];
+        z2.next_in = const_cast<Bytef*>(&file[idat_chunks[bi + 1].first]);
         z2.avail_in = (uInt)idat_chunks[bi + 1].second;
         z2.next_out = buf.data();
         z2.avail_out = (uInt)buf.size();

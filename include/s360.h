@@ -532,4 +532,5 @@ int s360_isp_config_tables(const s360_isp_config* cfg, float* ccm9, float* lut, 
 #endif
 #include "s360_cubemap.h" /* per-frame cubemap output of the stream / batch hosts */
 #include "s360_state_png.h" /* RGBA and batched PNG encode: the state images of a frame */
+#include "s360_png_decode.h" /* ... and their decode on the device: previous-frame state handed in as files */
 #endif /* S360_H_ */

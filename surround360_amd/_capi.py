@@ -95,6 +95,11 @@ STATE_PNG_SYMBOLS = [
     "s360_png_bound_c", "s360_encode_png_c", "s360_encode_png_batch",
     "s360_frame_encode_state_pngs", "s360_frame_state_png_bound", "s360_frame_download_state_png",
 ]
+# ... and every symbol include/s360_png_decode.h declares (banded PNG files decoded on the device; s360.h includes that header too)
+PNG_DECODE_SYMBOLS = [
+    "s360_png_decodable", "s360_decode_png_batch", "s360_png_decode_stats", "s360_png_decode_round_histogram", "s360_png_decode_failure",
+    "s360_frame_set_prev_images_png", "s360_frame_set_prev_flow",
+]
 # ... and the test taps include/s360_debug.h declares (not part of the API)
 DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
 
@@ -140,6 +145,22 @@ def lib():
         L.s360_frame_state_png_bound.argtypes = [C.c_void_p, C.c_int]
         L.s360_frame_download_state_png.restype = C.c_int
         L.s360_frame_download_state_png.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.s360_png_decodable.restype = C.c_int
+        L.s360_png_decodable.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.s360_decode_png_batch.restype = C.c_int
+        L.s360_decode_png_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                            C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+        L.s360_png_decode_stats.restype = C.c_int
+        L.s360_png_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.s360_png_decode_round_histogram.restype = C.c_int
+        L.s360_png_decode_round_histogram.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.s360_png_decode_failure.restype = C.c_int
+        L.s360_png_decode_failure.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.s360_frame_set_prev_images_png.restype = C.c_int
+        L.s360_frame_set_prev_images_png.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_size_t)]
+        L.s360_frame_set_prev_flow.restype = C.c_int
+        L.s360_frame_set_prev_flow.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
         L.s360_isp_config_defaults.restype = None
         L.s360_isp_destroy.restype = None
         L.s360_isp_destroy.argtypes = [C.c_void_p]

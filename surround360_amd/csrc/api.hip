@@ -758,6 +758,7 @@ int s360_frame_set_prev_pole_removal(s360_ctx* c, const float* flow, const uint8
     h2d(c, F.prFlow[prv].p, flow, n * sizeof(float2));
     S360_HIP(hipStreamSynchronize(c->st));
     F.have_prev_pr = true;
+    F.prevPrGot = 0;  // (halves handed in through s360_frame_set_prev_images_png / _flow are superseded)
   });
 }
 int s360_frame_render_pairs(s360_ctx* c, int p0, int p1, int use_prev) {
@@ -815,6 +816,7 @@ int s360_frame_set_prev_side(s360_ctx* c, int pair, const float* flow_l_to_r, co
     h2d(c, F.sideFlows.as<float2>() + on * j, flow_l_to_r, on * sizeof(float2));
     h2d(c, F.sideFlows.as<float2>() + on * (n + j), flow_r_to_l, on * sizeof(float2));
     S360_HIP(hipStreamSynchronize(c->st));  // the caller's buffers may be reused as soon as this returns
+    if ((size_t)pair < F.prevSideGot.size()) F.prevSideGot[(size_t)pair] = 0;  // (halves of this pair handed in as files are superseded)
     F.have_prev_side = true;
   });
 }
@@ -839,6 +841,7 @@ int s360_frame_set_prev_pole(s360_ctx* c, int unit, const float* flow, const uin
     F.poleRowsT = c->g.top_rows;
     F.poleRowsB = c->g.bottom_rows;
     F.have_prev_pole = true;
+    F.prevPoleGot[unit] = 0;  // (halves of this unit handed in as files are superseded)
   });
 }
 int s360_comm_get_unique_id(void* id_out) {
@@ -1480,6 +1483,229 @@ size_t s360_frame_state_png_bound(s360_ctx* c, int i) {
 int s360_frame_download_state_png(s360_ctx* c, int i, uint8_t* out, size_t cap, size_t* n_out) {
   if (!c) return S360_ERR_INVALID_ARG;
   return guard_l(c, [&](std::unique_lock<std::recursive_mutex>& lk) { png_batch_fetch(c, lk, c->statePng, i, out, cap, n_out, true); });
+}
+/* ---- banded PNG files decoded on the device (include/s360_png_decode.h, png_decode.hip) ---- */
+static const char* const kNotDecodable = "not a banded PNG file of this decoder";
+int s360_png_decodable(const uint8_t* file, size_t n, int whc[3], int* band_rows) {
+  return guard(nullptr, [&] {
+    need(whc && band_rows, "bad argument");
+    PngBandedInfo I;
+    if (!png_parse_banded(file, n, I)) throw Error(S360_ERR_INVALID_ARG, kNotDecodable);
+    whc[0] = I.w; whc[1] = I.h; whc[2] = I.channels;
+    *band_rows = I.band_rows;
+  });
+}
+// the files of a call parsed; throws naming the first image that is not this decoder's
+// a decode call fails because of file `image`: remembered for s360_png_decode_failure
+[[noreturn]] static void png_fail(s360_ctx* c, int image, int reason, const std::string& msg) {
+  c->pngDecFailImage = image;
+  c->pngDecFailReason = reason;
+  throw Error(S360_ERR_INVALID_ARG, msg);
+}
+static std::vector<PngBandedInfo> png_parse_all(s360_ctx* c, int n, const uint8_t* const* files, const size_t* bytes) {
+  c->pngDecFailImage = -1;
+  c->pngDecFailReason = S360_PNG_DECODE_FAILURE_NONE;
+  std::vector<PngBandedInfo> info((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    need(files[i] != nullptr, "bad argument");
+    if (!png_parse_banded(files[i], bytes[i], info[(size_t)i]))
+      png_fail(c, i, S360_PNG_DECODE_FAILURE_NOT_DECODABLE, "png decode: image " + std::to_string(i) + ": " + kNotDecodable);
+  }
+  return info;
+}
+// the launch sequence; a damaged file is remembered for s360_png_decode_failure
+static void png_decode_checked(s360_ctx* c, int n, const uint8_t* const* files, const std::vector<PngBandedInfo>& info, const std::vector<uint8_t*>& dst) {
+  try {
+    png_decode_run(c->st, c->pngDec, std::vector<const uint8_t*>(files, files + n), info, dst, c->pngDecStats, &c->prof);
+  } catch (const PngDecodeError& e) {
+    c->pngDecFailImage = e.image;
+    c->pngDecFailReason = S360_PNG_DECODE_FAILURE_DAMAGED;
+    throw;
+  }
+}
+int s360_png_decode_failure(s360_ctx* c, int* image, int* reason) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard(c, [&] {
+    need(image && reason, "bad argument");
+    *image = c->pngDecFailImage;
+    *reason = c->pngDecFailReason;
+  });
+}
+int s360_decode_png_batch(s360_ctx* c, int n, const uint8_t* const* files, const size_t* bytes, uint8_t* const* out, const size_t* cap,
+                          int* whc_out) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard_l(c, [&](std::unique_lock<std::recursive_mutex>&) {
+    need(n > 0 && n <= 4096 && files && bytes && out && cap, "bad argument");
+    const std::vector<PngBandedInfo> info = png_parse_all(c, n, files, bytes);
+    std::vector<size_t> at;
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+      const PngBandedInfo& I = info[(size_t)i];
+      const size_t nb = (size_t)I.w * I.h * I.channels;
+      need(out[i] != nullptr, "bad argument");
+      if (cap[i] < nb) png_fail(c, i, S360_PNG_DECODE_FAILURE_MISMATCH, "png decode: image " + std::to_string(i) + ": output buffer too small");
+      at.push_back(total);
+      total += (nb + 15) & ~(size_t)15;
+    }
+    c->op_a.ensure(total);
+    std::vector<uint8_t*> dst;
+    for (int i = 0; i < n; ++i) dst.push_back(c->op_a.as<uint8_t>() + at[(size_t)i]);
+    png_decode_checked(c, n, files, info, dst);
+    for (int i = 0; i < n; ++i) {
+      const PngBandedInfo& I = info[(size_t)i];
+      S360_HIP(hipMemcpyAsync(out[i], dst[(size_t)i], (size_t)I.w * I.h * I.channels, hipMemcpyDeviceToHost, c->st));
+      if (whc_out) { whc_out[3 * i] = I.w; whc_out[3 * i + 1] = I.h; whc_out[3 * i + 2] = I.channels; }
+    }
+    S360_HIP(hipStreamSynchronize(c->st));
+  }, false);
+}
+int s360_png_decode_stats(s360_ctx* c, uint64_t out[4]) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard(c, [&] {
+    need(out != nullptr, "bad argument");
+    for (int k = 0; k < 4; ++k) out[k] = c->pngDecStats[k];
+  });
+}
+int s360_png_decode_round_histogram(s360_ctx* c, uint64_t hist[66]) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard(c, [&] {
+    need(hist != nullptr, "bad argument");
+    for (int k = 0; k < 66; ++k) hist[k] = c->pngDecStats[4 + k];
+  });
+}
+// A set of previous-state halves is complete: mark the state as handed in, exactly as s360_frame_set_prev_side / _pole /
+// _pole_removal leave it.
+static void prev_side_arrived(FrameState& F, int pair, unsigned bits) {
+  if (F.prevSideGot.size() < (size_t)F.P) F.prevSideGot.resize((size_t)F.P, 0);
+  unsigned char& g = F.prevSideGot[(size_t)pair];
+  g |= (unsigned char)bits;
+  if (g == 15) { g = 0; F.have_prev_side = true; }
+}
+static void prev_pole_arrived(s360_ctx* c, FrameState& F, int unit, unsigned bits) {
+  unsigned char& g = F.prevPoleGot[unit];
+  g |= (unsigned char)bits;
+  if (g == 7) {
+    g = 0;
+    F.extW = int(float(c->P.eqr_width) * 1.2f);
+    F.extStride = (size_t)F.extW * std::max(c->g.top_rows, c->g.bottom_rows);
+    F.poleRowsT = c->g.top_rows;
+    F.poleRowsB = c->g.bottom_rows;
+    F.have_prev_pole = true;
+  }
+}
+static void prev_pr_arrived(FrameState& F, unsigned bits) {
+  F.prevPrGot |= (unsigned char)bits;
+  if (F.prevPrGot == 7) { F.prevPrGot = 0; F.have_prev_pr = true; }
+}
+// the block of pairs the previous side state is laid out for (as s360_frame_set_prev_side)
+static void prev_side_block(FrameState& F, int pair, int& j, int& n) {
+  need(pair >= 0 && pair < F.P, "pair_idx out of range");
+  if (!F.partition_declared) { F.side_p0 = 0; F.side_p1 = F.P; }
+  need(pair >= F.side_p0 && pair < F.side_p1, "pair_idx outside the block declared with s360_frame_set_partition");
+  j = pair - F.side_p0;
+  n = F.side_p1 - F.side_p0;
+}
+int s360_frame_set_prev_images_png(s360_ctx* c, int n, const char* const* names, const int* idx, const uint8_t* const* files,
+                                   const size_t* bytes) {
+  return frame_guard(c, [&] {
+    need(c && n > 0 && n <= 4096 && names && idx && files && bytes, "bad argument");
+    FrameState& F = frame_state(c);
+    const std::vector<PngBandedInfo> info = png_parse_all(c, n, files, bytes);
+    const size_t on = (size_t)c->g.overlap_image_width * c->g.cam_image_height;
+    const int extW = int(float(c->P.eqr_width) * 1.2f);
+    const size_t xs = (size_t)extW * std::max(c->g.top_rows, c->g.bottom_rows);
+    // where every image goes, and what it must look like; the buffers are sized as the raw-pixel calls size them
+    struct Arrival { int kind, k; unsigned bits; };  // kind 0 pair, 1 pole unit, 2 pole removal
+    std::vector<uint8_t*> dst;
+    std::vector<Arrival> arr;
+    int prW = 0, prH = 0;
+    for (int i = 0; i < n; ++i) {
+      need(names[i] != nullptr, "bad argument");
+      const std::string nm(names[i]);
+      const PngBandedInfo& I = info[(size_t)i];
+      int w = 0, h = 0;
+      uchar4* p = nullptr;
+      if (nm == "overlap_l" || nm == "overlap_r") {
+        int j = 0, nloc = 0;
+        prev_side_block(F, idx[i], j, nloc);
+        F.overlaps[F.last_side].ensure(2 * nloc * on * sizeof(uchar4));
+        w = c->g.overlap_image_width; h = c->g.cam_image_height;
+        p = F.overlaps[F.last_side].as<uchar4>() + on * (size_t)(nm == "overlap_r" ? nloc + j : j);
+        arr.push_back({0, idx[i], nm == "overlap_r" ? 2u : 1u});
+      } else if (nm == "extended_side" || nm == "extended_fisheye") {
+        need(idx[i] >= 0 && idx[i] < 4, "pole unit out of range");
+        F.extImgs[F.last_pole].ensure(6 * xs * sizeof(uchar4));
+        w = extW; h = idx[i] < 2 ? c->g.top_rows : c->g.bottom_rows;
+        p = F.extImgs[F.last_pole].as<uchar4>() + xs * (size_t)(nm == "extended_side" ? idx[i] : (idx[i] < 2 ? 4 : 5));
+        arr.push_back({1, idx[i], nm == "extended_side" ? 1u : 2u});
+      } else if (nm == "bottom_image" || nm == "bottom_image2") {
+        need(c->P.enable_pole_removal != 0, "this context does not run pole removal");
+        if (!prW) { prW = I.w; prH = I.h; }
+        const size_t pn = (size_t)prW * prH;
+        F.prImgs[F.last_pr].ensure(2 * pn * sizeof(uchar4));
+        w = prW; h = prH;
+        if (F.poleW > 0 && (F.poleW != prW || F.poleH != prH))
+          png_fail(c, i, S360_PNG_DECODE_FAILURE_MISMATCH, "png decode: image " + std::to_string(i) + " (" + nm + "): not the size of the bottom camera's image");
+        p = F.prImgs[F.last_pr].as<uchar4>() + (nm == "bottom_image2" ? pn : 0);
+        arr.push_back({2, 0, nm == "bottom_image2" ? 2u : 1u});
+      } else {
+        throw Error(S360_ERR_INVALID_ARG, "not a previous-state image name: " + nm);
+      }
+      if (I.channels != 4 || I.w != w || I.h != h)
+        png_fail(c, i, S360_PNG_DECODE_FAILURE_MISMATCH, "png decode: image " + std::to_string(i) + " (" + nm + "): wrong size/channels for the previous state");
+      dst.push_back(reinterpret_cast<uint8_t*>(p));
+    }
+    // (a later ensure() of a buffer an earlier image of this call points into would move it: sizes per buffer are the same for
+    // every image of a kind, except pole removal, whose size the first such image fixes)
+    png_decode_checked(c, n, files, info, dst);
+    for (const Arrival& a : arr) {
+      if (a.kind == 0) prev_side_arrived(F, a.k, a.bits);
+      else if (a.kind == 1) {
+        // the fisheye image is shared by the two units of a pole
+        if (a.bits == 2u) { prev_pole_arrived(c, F, a.k, 2u); prev_pole_arrived(c, F, a.k ^ 1, 2u); }
+        else prev_pole_arrived(c, F, a.k, 1u);
+      } else {
+        F.prevPrW = prW; F.prevPrH = prH;
+        prev_pr_arrived(F, a.bits);
+      }
+    }
+  });
+}
+int s360_frame_set_prev_flow(s360_ctx* c, const char* name, int idx, const float* flow) {
+  return frame_guard(c, [&] {
+    need(c && name && flow, "bad argument");
+    FrameState& F = frame_state(c);
+    const std::string nm(name);
+    if (nm == "flow_l_to_r" || nm == "flow_r_to_l") {
+      int j = 0, nloc = 0;
+      prev_side_block(F, idx, j, nloc);
+      const size_t on = (size_t)c->g.overlap_image_width * c->g.cam_image_height;
+      F.sideFlows.ensure(2 * nloc * on * sizeof(float2));
+      h2d(c, F.sideFlows.as<float2>() + on * (size_t)(nm == "flow_r_to_l" ? nloc + j : j), flow, on * sizeof(float2));
+      S360_HIP(hipStreamSynchronize(c->st));
+      prev_side_arrived(F, idx, nm == "flow_r_to_l" ? 8u : 4u);
+    } else if (nm == "flow_pole") {
+      need(idx >= 0 && idx < 4, "pole unit out of range");
+      const int extW = int(float(c->P.eqr_width) * 1.2f);
+      const size_t xs = (size_t)extW * std::max(c->g.top_rows, c->g.bottom_rows);
+      const size_t xn = (size_t)extW * (idx < 2 ? c->g.top_rows : c->g.bottom_rows);
+      F.poleFlows.ensure(4 * xs * sizeof(float2));
+      h2d(c, F.poleFlows.as<float2>() + xs * (size_t)idx, flow, xn * sizeof(float2));
+      S360_HIP(hipStreamSynchronize(c->st));
+      prev_pole_arrived(c, F, idx, 4u);
+    } else if (nm == "flow_bottom_secondary") {
+      need(c->P.enable_pole_removal != 0, "this context does not run pole removal");
+      const int w = F.prevPrW > 0 ? F.prevPrW : F.poleW, h = F.prevPrW > 0 ? F.prevPrH : F.poleH;
+      if (w <= 0 || h <= 0) throw Error(S360_ERR_STATE, "flow_bottom_secondary: the bottom images' size is not known yet (hand bottom_image / bottom_image2 in first)");
+      const size_t pn = (size_t)w * h;
+      F.prFlow[F.last_pr].ensure(pn * sizeof(float2));
+      h2d(c, F.prFlow[F.last_pr].p, flow, pn * sizeof(float2));
+      S360_HIP(hipStreamSynchronize(c->st));
+      prev_pr_arrived(F, 4u);
+    } else {
+      throw Error(S360_ERR_INVALID_ARG, "not a previous-state flow name: " + nm);
+    }
+  });
 }
 int s360_frame_get_f32(s360_ctx* c, const char* name, int idx, int whc[3], float* dst) {
   return frame_guard(c, [&] {

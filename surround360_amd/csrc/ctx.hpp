@@ -8,6 +8,7 @@
 #include "core.hpp"
 #include "flow.hpp"
 #include "png.hpp"
+#include "png_decode.hpp"
 #include "rig.hpp"
 
 namespace s360 {
@@ -62,6 +63,10 @@ struct s360_ctx {
     unsigned long long gen = 0;
   };
   PngBatch statePng, opPng;
+  // the PNG decoder (png_decode.hip): its buffers (grow only) and the counters of the last decode call on this context
+  s360::PngDecodeBufs pngDec;
+  unsigned long long pngDecStats[s360::kPngDecodeStatWords] = {0};
+  int pngDecFailImage = -1, pngDecFailReason = 0;  // s360_png_decode_failure: of the last decode call
   hipEvent_t evUpHost = nullptr; // s360_frame_uploads_complete
   static constexpr int kPinChunks = 4;
   static constexpr size_t kPinChunkBytes = (size_t)8 << 20;

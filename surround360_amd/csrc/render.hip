@@ -449,6 +449,7 @@ static void dev_pole_removal(s360_ctx* c, FrameState& F, bool use_prev) {
   }
   F.have_prev_pr = true;
   F.last_pr = cur;
+  F.prevPrGot = 0;  // (halves of a hand-over in two calls do not outlive a rendered frame: api.hip)
 }
 
 static void ensure_maps(s360_ctx* c) {
@@ -638,6 +639,7 @@ static void side_stage(s360_ctx* c, const std::vector<int>& slotIds, int p0, int
     F.side_p1 = p1;
     F.have_prev_side = true;
     F.last_side = cur;
+    F.prevSideGot.clear();
   }
   if (c->pipeline) S360_HIP(hipEventRecord(c->evSideDone, st));
 }
@@ -885,6 +887,7 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
       F.poleRowsB = rowsB;
       F.have_prev_pole = true;
       F.last_pole = cur;
+      for (unsigned char& got : F.prevPoleGot) got = 0;
     }
     if (!(phases & 2)) continue;
     {

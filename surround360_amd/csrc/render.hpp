@@ -95,6 +95,12 @@ struct FrameState {
   }
   int cur_side = 0, cur_pole = 0, last_side = 0, last_pole = 0;
   bool have_prev_side = false, have_prev_pole = false;
+  // previous state handed in in halves (s360_frame_set_prev_images_png / s360_frame_set_prev_flow): what has arrived so far per
+  // pair (bits: overlap_l, overlap_r, flow_l_to_r, flow_r_to_l), per pole unit (extended_side, extended_fisheye, flow_pole) and for
+  // pole removal (bottom_image, bottom_image2, flow_bottom_secondary); a complete set marks the state as handed in and is cleared
+  std::vector<unsigned char> prevSideGot;
+  unsigned char prevPoleGot[4] = {0, 0, 0, 0}, prevPrGot = 0;
+  int prevPrW = 0, prevPrH = 0;  // size of the pole-removal images handed in as files
   bool keep_intermediates = false;  // copy panoramas before the pole composite (parity tests)
   DevBuf panoDbg[2];
   int extW = 0, poleRowsT = 0, poleRowsB = 0;  // geometry the pole temporal state was produced with

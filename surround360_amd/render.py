@@ -485,6 +485,62 @@ class Context:
         self._ck(lib().s360_frame_download_state_png(self.h, int(i), _p(out), C.c_size_t(out.size), C.byref(n)))
         return out[:n.value]
 
+    def decode_png_batch(self, files, caps=None, outs=None):
+        """s360_decode_png_batch: a list of banded PNG files (bytes) -> the list of their images, (h, w, 3) B,G,R or (h, w, 4)
+        B,G,R,A uint8 arrays, decoded by one launch sequence on the device. `caps`: output buffer sizes to offer instead of the
+        images' own (a smaller one is refused); `outs`: uint8 buffers to decode into (default: new ones of those sizes)."""
+        k = len(files)
+        assert k > 0
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        whc = []
+        for f in bufs:
+            d = png_decodable(f)
+            whc.append(d[:3] if d else (0, 0, 0))
+        sizes = [w * h * c for w, h, c in whc] if caps is None else [int(v) for v in caps]
+        if outs is None:
+            outs = [np.empty(max(n, 1), np.uint8) for n in sizes]
+        got = (C.c_int * (3 * k))()
+        self._ck(lib().s360_decode_png_batch(
+            self.h, k, (C.c_void_p * k)(*[b.ctypes.data for b in bufs]), (C.c_size_t * k)(*[b.size for b in bufs]),
+            (C.c_void_p * k)(*[o.ctypes.data for o in outs]), (C.c_size_t * k)(*sizes), got))
+        return [o[:got[3 * i] * got[3 * i + 1] * got[3 * i + 2]].reshape(got[3 * i + 1], got[3 * i], got[3 * i + 2]) for i, o in enumerate(outs)]
+
+    def png_decode_stats(self):
+        """s360_png_decode_stats: (fast-path bands, general-path bands, stored-only bands, most speculation rounds) of the last
+        decode call on this context."""
+        v = (C.c_uint64 * 4)()
+        self._ck(lib().s360_png_decode_stats(self.h, v))
+        return tuple(int(x) for x in v)
+
+    def png_decode_round_histogram(self):
+        """hist[r] = fast-path bands of the last decode call whose slowest window took r speculation rounds (66 entries)."""
+        v = (C.c_uint64 * 66)()
+        self._ck(lib().s360_png_decode_round_histogram(self.h, v))
+        return [int(x) for x in v]
+
+    def png_decode_failure(self):
+        """s360_png_decode_failure: (image index or -1, reason) of the last decode call — reason 0 none, 1 not a file of this decoder,
+        2 size / channels / buffer mismatch, 3 damaged."""
+        image, reason = C.c_int(-1), C.c_int(0)
+        self._ck(lib().s360_png_decode_failure(self.h, C.byref(image), C.byref(reason)))
+        return image.value, reason.value
+
+    def set_prev_images_png(self, names_idx, files):
+        """s360_frame_set_prev_images_png: banded PNG files decoded straight into the previous-state image buffers. names_idx: a
+        list of (name, idx) with the names of encode_state_pngs; files: their bytes."""
+        k = len(names_idx)
+        assert k == len(files) and k > 0
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        names = (C.c_char_p * k)(*[n.encode() for n, _ in names_idx])
+        self._ck(lib().s360_frame_set_prev_images_png(
+            self.h, k, names, (C.c_int * k)(*[int(i) for _, i in names_idx]), (C.c_void_p * k)(*[b.ctypes.data for b in bufs]),
+            (C.c_size_t * k)(*[b.size for b in bufs])))
+
+    def set_prev_flow(self, name, idx, flow):
+        """s360_frame_set_prev_flow: one previous-frame flow (the names of get_f32) as (h, w, 2) float32."""
+        flow = np.ascontiguousarray(flow, np.float32)
+        self._ck(lib().s360_frame_set_prev_flow(self.h, name.encode(), int(idx), _p(flow)))
+
     def uploads_complete(self):
         """Blocks until every upload enqueued so far has left its host buffer (needed for buffers from pinned_empty only)."""
         self._ck(lib().s360_frame_uploads_complete(self.h))
@@ -652,3 +708,14 @@ class StereoPanoramaRenderer:
         self.ctx.upload_frame(side_images, top_image, bottom_image)
         self.ctx.render(use_prev)
         return self.ctx.download_equirect()
+
+
+def png_decodable(file):
+    """s360_png_decodable (host only): (w, h, channels, band_rows) if `file` (bytes) is a banded PNG the device decoder takes, else
+    None."""
+    b = np.frombuffer(bytes(file), np.uint8) if not isinstance(file, np.ndarray) else file
+    whc = (C.c_int * 3)()
+    rows = C.c_int(0)
+    if lib().s360_png_decodable(b.ctypes.data if b.size else None, C.c_size_t(b.size), whc, C.byref(rows)) != 0:
+        return None
+    return whc[0], whc[1], whc[2], rows.value
