@@ -119,13 +119,18 @@ __global__ __launch_bounds__(256) void k_resize_cubic_u8c4(const uchar4* __restr
 constexpr int HR_TW = 256, HR_TH = 16, HR_BW = 320;
 typedef unsigned u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));  // (rows start at any 4-byte address)
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// BGR: the final resize itself. The reference resizes 3-channel eyes there, and the output is the packed B,G,R image (row
+// pitch 3 dw bytes) the frame's finish stage would otherwise make of a uchar4 output with k_pack_bgr. A thread's 4 pixels
+// are 12 bytes: three 4-byte words where dst and the row pitch are multiples of 4 (ALIGNED), single bytes otherwise.
+template <bool BGR, bool ALIGNED>
 __global__ __launch_bounds__(256) void k_resize_cubic_u8c4_h(const uchar4* __restrict__ src, int sw, int h, size_t sbs,
-                                                             uchar4* __restrict__ dst, int dw, size_t dbs, double scx) {
+                                                             void* __restrict__ dst, int dw, size_t dbs, double scx) {
   __shared__ __attribute__((aligned(16))) unsigned s_box[HR_TH][HR_BW];
   const int tid = threadIdx.x, cx = tid & 63, q = tid >> 6;
   const int tx0 = blockIdx.x * HR_TW, ty0 = blockIdx.y * HR_TH;
   const unsigned* S = reinterpret_cast<const unsigned*>(src + sbs * blockIdx.z);
-  unsigned* D = reinterpret_cast<unsigned*>(dst + dbs * blockIdx.z);
+  unsigned* D = BGR ? nullptr : reinterpret_cast<unsigned*>(static_cast<uchar4*>(dst) + dbs * blockIdx.z);
+  uint8_t* D3 = BGR ? static_cast<uint8_t*>(dst) + dbs * blockIdx.z : nullptr;
   // the box: columns bx0 (16-byte piece of the first column's first tap) .. the last column's last tap
   int s0, s1;
   float f;
@@ -173,6 +178,11 @@ __global__ __launch_bounds__(256) void k_resize_cubic_u8c4_h(const uchar4* __res
   }
   __syncthreads();
   if (dx0 >= dw) return;
+  // the SSE2 path covers whole groups of 8 ELEMENTS of the reference's row: of its 4-channel rows that is every pixel but an
+  // odd last one; the final resize runs on 3-channel eyes (TRSP:888-894 flattens them), so there the tail is the last
+  // 3 dw % 8 elements, which can begin in the middle of a pixel
+  constexpr int CN = BGR ? 3 : 4;
+  const int vec_end = dw * CN / 8 * 8;
 #pragma unroll
   for (int r = 0; r < HR_TH / 4; ++r) {
     const int row = q * (HR_TH / 4) + r, dy = ty0 + row;
@@ -181,10 +191,10 @@ __global__ __launch_bounds__(256) void k_resize_cubic_u8c4_h(const uchar4* __res
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const unsigned p0 = s_box[row][c[j][0]], p1 = s_box[row][c[j][1]], p2 = s_box[row][c[j][2]], p3 = s_box[row][c[j][3]];
-      const bool sse = dx0 + j < (dw & ~1);
       o[j] = 0;
 #pragma unroll
-      for (int ch = 0; ch < 4; ++ch) {
+      for (int ch = 0; ch < CN; ++ch) {
+        const bool sse = (dx0 + j) * CN + ch < vec_end;
         const unsigned sel = 0x0c040c00u + ch * 0x00010001u;
         const s16x2 lo = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(p1, p0, sel));
         const s16x2 hi = __builtin_bit_cast(s16x2, __builtin_amdgcn_perm(p3, p2, sel));
@@ -194,6 +204,25 @@ __global__ __launch_bounds__(256) void k_resize_cubic_u8c4_h(const uchar4* __res
         const int v = sse ? (int)__builtin_rintf((float)h1 * (1.f / 2048)) : (h1 * 2048 + (1 << 21)) >> 22;
         o[j] |= (unsigned)sat_u8(v) << (8 * ch);
       }
+    }
+    if (BGR) {
+      uint8_t* Db = D3 + ((size_t)dy * dw + dx0) * 3;
+      if (ALIGNED && dx0 + 3 < dw) {
+        unsigned* Dw = reinterpret_cast<unsigned*>(Db);  // (three words, not a 3-vector: that type is 16 bytes wide)
+        Dw[0] = (o[0] & 0xffffffu) | (o[1] << 24);
+        Dw[1] = ((o[1] >> 8) & 0xffffu) | (o[2] << 16);
+        Dw[2] = ((o[2] >> 16) & 0xffu) | (o[3] << 8);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (dx0 + j < dw) {
+            Db[3 * j] = (uint8_t)o[j];
+            Db[3 * j + 1] = (uint8_t)(o[j] >> 8);
+            Db[3 * j + 2] = (uint8_t)(o[j] >> 16);
+          }
+        }
+      }
+      continue;
     }
     unsigned* Dr = D + (size_t)dy * dw + dx0;
     if (dx0 + 3 < dw) {
@@ -1106,8 +1135,8 @@ void launch_resize_cubic_u8c4(hipStream_t st, const uchar4* src, int sw, int sh,
   // same height: one source row per output row (k_resize_cubic_u8c4_h), where a 256-column tile's source box fits (its
   // taps span at most ceil(255 * scx) + 1 + 3 columns, the box starts up to 3 columns early and ends on a whole piece)
   if (sh == dh && !src_tab && known_result_enabled() && (int)std::ceil((HR_TW - 1) * scx) + 12 <= HR_BW) {
-    hipLaunchKernelGGL(k_resize_cubic_u8c4_h, dim3((dw + HR_TW - 1) / HR_TW, (dh + HR_TH - 1) / HR_TH, B), dim3(256), 0, st,
-                       src, sw, sh, sbs, dst, dw, dbs, scx);
+    hipLaunchKernelGGL((k_resize_cubic_u8c4_h<false, false>), dim3((dw + HR_TW - 1) / HR_TW, (dh + HR_TH - 1) / HR_TH, B), dim3(256),
+                       0, st, src, sw, sh, sbs, (void*)dst, dw, dbs, scx);
     return;
   }
   if (resize_cubic_u8c4_tiled_fits(sw, sh, dw, dh)) {
@@ -1116,6 +1145,18 @@ void launch_resize_cubic_u8c4(hipStream_t st, const uchar4* src, int sw, int sh,
     return;
   }
   launch_resize_cubic_u8c4_generic(st, src, sw, sh, sbs, dst, dw, dh, dbs, B, src_tab);
+}
+// The same-height resize with the packed B,G,R image as its output (one image). false, and nothing launched, where
+// launch_resize_cubic_u8c4 would not take k_resize_cubic_u8c4_h for the shape: the caller then resizes and packs in two steps.
+bool launch_resize_cubic_u8c4_to_bgr(hipStream_t st, const uchar4* src, int sw, int sh, uint8_t* dst_bgr, int dw, int dh) {
+  const double scx = 1.0 / ((double)dw / (double)sw);
+  if (!(sh == dh && known_result_enabled() && (int)std::ceil((HR_TW - 1) * scx) + 12 <= HR_BW)) return false;
+  const dim3 grid((dw + HR_TW - 1) / HR_TW, (dh + HR_TH - 1) / HR_TH, 1);
+  if ((dw & 3) == 0 && (reinterpret_cast<uintptr_t>(dst_bgr) & 3) == 0)
+    hipLaunchKernelGGL((k_resize_cubic_u8c4_h<true, true>), grid, dim3(256), 0, st, src, sw, sh, (size_t)0, (void*)dst_bgr, dw, (size_t)0, scx);
+  else
+    hipLaunchKernelGGL((k_resize_cubic_u8c4_h<true, false>), grid, dim3(256), 0, st, src, sw, sh, (size_t)0, (void*)dst_bgr, dw, (size_t)0, scx);
+  return true;
 }
 // PixFlow's entry (PixFlow.h:98-135): the downscaled image's grey and alpha planes; the image itself only where `down` is given.
 // Where the tiled resize does not fit, the generic resize writes the image to `scratch` and k_gray_alpha reads it back.

@@ -37,6 +37,8 @@ extern unsigned long long g_known_stats[2];
 // live in one allocation); likewise dst_tab / src_tab of the other launchers that take one.
 void launch_resize_cubic_u8c4(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* dst, int dw,
                               int dh, size_t dbs, int B, const uchar4* const* src_tab = nullptr);
+// the resize of one image straight into packed B,G,R where the same-height kernel takes the shape (false otherwise: nothing is launched)
+bool launch_resize_cubic_u8c4_to_bgr(hipStream_t st, const uchar4* src, int sw, int sh, uint8_t* dst_bgr, int dw, int dh);
 // the one-thread-per-pixel kernel whatever the shape (launch_resize_cubic_u8c4's fallback; the tests' second opinion)
 void launch_resize_cubic_u8c4_generic(hipStream_t st, const uchar4* src, int sw, int sh, size_t sbs, uchar4* dst, int dw,
                                       int dh, size_t dbs, int B, const uchar4* const* src_tab = nullptr);

@@ -915,8 +915,8 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
   if (!(phases & 2)) return;
   // sharpenThread for the eyes of several slots per set of launches (TRSP:901-915 runs the two eyes on two threads): the
   // IIR passes are one serial chain per (row, channel) — the 2 x 4096 rows of one frame are 512 waves, half a wave per
-  // SIMD — so the slots of a batch are sharpened in groups of four (8 images: 2 waves per SIMD cover each other's
-  // dependent chains), group after group, all groups through the same scratch (SlotScratch)
+  // SIMD — so the slots of a batch are sharpened in groups of SlotScratch::kSharpenGroup images (several waves per SIMD
+  // cover each other's dependent chains), group after group, all groups through the same scratch (SlotScratch)
   if (c->P.sharpening > 0.0) {
     ProfScope ps(prof, "finish");
     std::vector<uchar4*> imgs;
@@ -983,12 +983,15 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
       const bool resize = (outW != W) || (eyeH != H);
       for (int e = 0; e < 2; ++e) {
         uchar4* eye = F.pano[e].as<uchar4>();
+        uint8_t* half = F.outBGR[ob].as<uint8_t>() + (size_t)e * outW * eyeH * 3;
+        // the 8k and 6k presets only change the width: that resize writes the output's B,G,R itself
+        if (resize && launch_resize_cubic_u8c4_to_bgr(st, eye, W, H, half, outW, eyeH)) continue;
         if (resize) {
           F.sc->eyeFinal[e].ensure((size_t)outW * eyeH * sizeof(uchar4));
           launch_resize_cubic_u8c4(st, eye, W, H, en, F.sc->eyeFinal[e].as<uchar4>(), outW, eyeH, (size_t)outW * eyeH, 1);
           eye = F.sc->eyeFinal[e].as<uchar4>();
         }
-        launch_pack_bgr(st, eye, outW, eyeH, F.outBGR[ob].as<uint8_t>() + (size_t)e * outW * eyeH * 3);
+        launch_pack_bgr(st, eye, outW, eyeH, half);
       }
       if (c->png_encode) {  // imwriteExceptionOnFail's PngEncoder (TRSP:938-961) on the device: png.hip
         ProfScope ps(prof, "png_encode");

@@ -39,10 +39,10 @@ struct SlotScratch {
   DevBuf warpPacked, warpTiles;  // this frame's pole warp as packed coordinates + tile boxes (launch_pole_warp_packed)
   DevBuf eyeFinal[2];
   DevBuf pngScratch;  // the device PNG encoder's per-band segments before they are gathered into a slot's file image (png.hip)
-  // the sharpen passes' low-pass image and float scratch for ONE group of kSharpenGroup images: the eyes of a batch are
-  // sharpened group after group on one stream (8 images = 4 slots' eyes are 2 waves per SIMD in the row passes: enough to
-  // cover each other's dependent chains), so the 1.1 GB per 8K slot these were is 4.4 GB per context
-  static constexpr int kSharpenGroup = 8;
+  // the sharpen passes' 8-bit low-pass image and checkpoint scratch for ONE group of kSharpenGroup images: the eyes of a
+  // batch are sharpened group after group on one stream. The passes keep no float image (render_kernels.hip, k_iir_pass),
+  // so a group costs 138 MB of low pass + 9 MB of checkpoints per 8K eye
+  static constexpr int kSharpenGroup = 32;
   DevBuf sharpLp[kSharpenGroup], sharpBuf[kSharpenGroup];
 };
 

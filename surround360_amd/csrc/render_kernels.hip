@@ -1660,13 +1660,20 @@ __device__ __forceinline__ int refl_i(int x, int r) { return x < 0 ? -x : x >= r
 __device__ __forceinline__ float clamp255(float v) { return v < 0.0f ? 0.0f : v > 255.0f ? 255.0f : v; }
 // iirLowPass is a first-order recurrence v = ip*(1-alpha) + v*alpha along every row (then every column), forwards
 // and backwards: bit-exactness forbids re-associating it, so the parallelism is one chain per (row, channel) — 16 384
-// chains for the row pass of a 4096-row eye — and each chain is 2 x 8400 dependent steps. The kernels below keep a
-// chain in one lane (a wave = 16 chains x 4 channels; the alpha lane computes a value nobody reads), move the data in
+// chains for the row pass of a 4096-row eye — and each chain is dependent steps end to end. The kernel below keeps a
+// chain in one lane (a wave = 16 chains x 4 channels; the alpha lane computes a value nobody reads), moves the data in
 // tiles of 64 positions through LDS so that global memory is only touched with coalesced row segments (row pass) or
-// whole 64/256-byte runs per lane (column pass), and prefetch the next tile while the current one is computed. The
-// causal pass writes its float results (float4 per pixel) and each chain's final state; the anticausal pass reads them
-// back in reverse and writes the clamped 8-bit low pass — or, for the last pass, the sharpened pixel itself
-// (sharpenWithIirLowPass, Filter.h:93-127, fused: the low pass is only ever used there).
+// whole 64/256-byte runs per lane (column pass), and prefetches the next tile while the current one is computed.
+//
+// One kernel per direction, both halves in the same wave (k_iir_pass). The anticausal half reads the causal half's float
+// values in reverse; no float image is kept for that. The forward phase only stores the chain state at every tile
+// boundary (one float per lane and tile, 0.25 bytes per pixel); the backward phase loads the 8-bit tile again, runs
+// the causal recurrence from the tile's checkpoint — the same operations on the same operands, so the same floats —
+// into the lane's own registers and then walks the tile backwards. The final causal value (what the anticausal half
+// starts from, and what a row reads at position -1) stays in a register between the phases, which is why the two
+// phases are one kernel: a lane reads back only the checkpoints it wrote itself. The anticausal half writes the
+// clamped 8-bit low pass — or, for the last pass, the sharpened pixel itself (sharpenWithIirLowPass, Filter.h:93-127,
+// fused: the low pass is only ever used there).
 constexpr int IIR_CH = 16;   // chains per wave
 constexpr int IIR_T = 64;    // positions per tile
 constexpr int IIR_LD = IIR_T + 1;  // padded LDS row: 16 chains hit 16 different banks
@@ -1675,11 +1682,11 @@ struct IirGeom {
   int nchains;  // ROWS: h, columns: w
   int w;        // image row pitch in pixels
 };
-constexpr int IIR_MAX_IMGS = 32;  // images per launch (blockIdx.y): the two eyes of every frame slot of a batch
+constexpr int IIR_MAX_IMGS = 32;  // images per launch (blockIdx.y): the two eyes of every frame slot of a group
 struct IirImgs {
   const uchar4* x[IIR_MAX_IMGS];  // input of the pass
   uchar4* out[IIR_MAX_IMGS];      // 8-bit output of the anticausal half
-  float4* buf[IIR_MAX_IMGS];      // float results of the causal half (+ carried state behind them)
+  float* ck[IIR_MAX_IMGS];        // chain states at the tile boundaries: [wave][tile][lane]
 };
 template <bool ROWS>
 __device__ __forceinline__ int iir_bnd(int x, int n) { return ROWS ? wrap_i(x, n) : refl_i(x, n); }
@@ -1687,35 +1694,27 @@ template <bool ROWS>
 __device__ __forceinline__ size_t iir_px(const IirGeom& g, int chain, int pos) {
   return ROWS ? (size_t)chain * g.w + pos : (size_t)pos * g.w + chain;
 }
+static inline size_t iir_tiles(int n) { return (size_t)(n + IIR_T - 1) / IIR_T; }
+static inline size_t iir_waves(int nchains) { return (size_t)(nchains + IIR_CH - 1) / IIR_CH; }
 
-// The float results of a causal half live in global memory until the anticausal half has read them: three floats per pixel
-// (B, G, R) — the alpha chain's value is never read, the output alpha is 255 (Filter.h:40-127 runs on 3-channel images) —
-// i.e. 12 + 12 instead of 16 + 16 bytes per pixel and pass pair.
-struct IirPx { float b, g, r; };
-__device__ __forceinline__ void iir_put(float* __restrict__ B, size_t px, float4 v) {
-  IirPx o{v.x, v.y, v.z};
-  *reinterpret_cast<IirPx*>(B + px * 3) = o;
-}
-typedef float iir_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ iir_f4 iir_get(const float* __restrict__ B, size_t px) {
-  const IirPx o = *reinterpret_cast<const IirPx*>(B + px * 3);
-  return iir_f4{o.b, o.g, o.r, 0.0f};
-}
-// Causal half: B[e] = v after consuming X[bnd(e+1)], e = 0..n-1, v0 = X[0]; carry[chain] = final v.
-template <bool ROWS>
-__global__ __launch_bounds__(64) void k_iir_causal(IirImgs im, IirGeom g, size_t npix, float alpha) {
+// Causal half: B[e] = v after consuming X[bnd(e+1)], e = 0..n-1, v0 = X[0].
+// Anticausal half: v = B[n-1]; for e = n-1 .. 0: v = lerp(B[bnd(e-1)], v); OUT[e] = clamp(v). FUSE: OUT is the unsharp
+// mask of the image in `out` against that low-pass value, written in place.
+template <bool ROWS, bool FUSE>
+__global__ __launch_bounds__(64) void k_iir_pass(IirImgs im, IirGeom g, float alpha, float amount) {
   const uchar4* __restrict__ X = im.x[blockIdx.y];
-  float* __restrict__ Bf = reinterpret_cast<float*>(im.buf[blockIdx.y]);
-  float* __restrict__ carry = Bf + npix * 3;
+  uchar4* __restrict__ out = im.out[blockIdx.y];
   __shared__ unsigned s_in[IIR_CH * IIR_LD];
-  __shared__ float s_out[IIR_CH * IIR_LD * 4];
+  __shared__ unsigned s_out[IIR_CH * IIR_LD];
   const int lane = threadIdx.x, k = lane >> 2, c = lane & 3;
   const int chain0 = blockIdx.x * IIR_CH;
   const int ntiles = (g.n + IIR_T - 1) / IIR_T;
+  float* __restrict__ ck = im.ck[blockIdx.y] + (size_t)blockIdx.x * ntiles * 64 + lane;
   unsigned pre[IIR_CH];
   // X at positions bnd(e + 1). ROWS: load kk is chain kk at e = 64 t + lane (256 contiguous bytes). Columns: a chain is a
   // column, so a load covers 4 image rows x the 16 chains (four 64-byte runs) — lane = (row lane >> 4 of the group, chain
-  // lane & 15), load i is rows 4 i .. 4 i + 3 of the tile — instead of one pixel from each of 64 rows.
+  // lane & 15), load i is rows 4 i .. 4 i + 3 of the tile — instead of one pixel from each of 64 rows. Positions behind
+  // the chain's end repeat its last one, so a ragged tile holds 64 real inputs all the same.
   const int cl = lane & 15, rl = lane >> 4;
   auto load_tile = [&](int t) {
     if (ROWS) {
@@ -1733,107 +1732,51 @@ __global__ __launch_bounds__(64) void k_iir_causal(IirImgs im, IirGeom g, size_t
       }
     }
   };
-  const float am = 1.0f - alpha;
-  float v;
-  {
-    const uchar4 p0 = X[iir_px<ROWS>(g, min(chain0 + k, g.nchains - 1), 0)];
-    v = c == 0 ? (float)p0.x : c == 1 ? (float)p0.y : c == 2 ? (float)p0.z : (float)p0.w;
-  }
-  load_tile(0);
-  for (int t = 0; t < ntiles; ++t) {
+  auto stage_tile = [&]() {
 #pragma unroll
     for (int kk = 0; kk < IIR_CH; ++kk) {
       if (ROWS) s_in[kk * IIR_LD + lane] = pre[kk];
       else s_in[cl * IIR_LD + 4 * kk + rl] = pre[kk];
     }
+  };
+  const float am = 1.0f - alpha;
+  const unsigned char* sb = reinterpret_cast<const unsigned char*>(s_in) + (size_t)k * IIR_LD * 4 + c;
+  float v;
+  {
+    const uchar4 p0 = X[iir_px<ROWS>(g, min(chain0 + k, g.nchains - 1), 0)];
+    v = c == 0 ? (float)p0.x : c == 1 ? (float)p0.y : c == 2 ? (float)p0.z : (float)p0.w;
+  }
+  // ---- forward: the causal half, of which only the state in front of every tile is kept
+  load_tile(0);
+  for (int t = 0; t < ntiles; ++t) {
+    ck[(size_t)t * 64] = v;
+    stage_tile();
     S360_WAVE_SYNC();  // (one wave per workgroup: the tile is written position-major and read chain-major)
     if (t + 1 < ntiles) load_tile(t + 1);
     const int cnt = min(IIR_T, g.n - t * IIR_T);
-    const unsigned char* sb = reinterpret_cast<const unsigned char*>(s_in) + (size_t)k * IIR_LD * 4 + c;
-    float* so = s_out + (size_t)k * IIR_LD * 4 + c;
     int j = 0;
     for (; j + 8 <= cnt; j += 8) {  // 8 inputs fetched together: the dependent chain is then 2 VALU ops per step
       float ip[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) ip[q] = (float)sb[(j + q) * 4] * am;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        v = ip[q] + v * alpha;  // lerp(ip, v, alpha) = ip*(1-alpha) + v*alpha, MathUtil.h
-        so[(j + q) * 4] = v;
-      }
+      for (int q = 0; q < 8; ++q) v = ip[q] + v * alpha;  // lerp(ip, v, alpha) = ip*(1-alpha) + v*alpha, MathUtil.h
     }
-    for (; j < cnt; ++j) {
-      v = (float)sb[j * 4] * am + v * alpha;
-      so[j * 4] = v;
-    }
+    for (; j < cnt; ++j) v = (float)sb[j * 4] * am + v * alpha;
     S360_WAVE_SYNC();
-    // store the tile's float results: ROWS: 1 KB per chain row; columns: four 256-byte runs (4 rows x 16 chains) per store
-    if (ROWS) {
-      const int e = t * IIR_T + lane;
-      if (e < g.n) {
-#pragma unroll
-        for (int kk = 0; kk < IIR_CH; ++kk) {
-          if (chain0 + kk < g.nchains) {
-            const float4 o = *reinterpret_cast<const float4*>(s_out + ((size_t)kk * IIR_LD + lane) * 4);
-            iir_put(Bf, iir_px<ROWS>(g, chain0 + kk, e), o);
-          }
-        }
-      }
-    } else if (chain0 + cl < g.nchains) {
-#pragma unroll
-      for (int i = 0; i < IIR_CH; ++i) {
-        const int p = 4 * i + rl, e = t * IIR_T + p;
-        if (e < g.n) iir_put(Bf, (size_t)e * g.w + chain0 + cl, *reinterpret_cast<const float4*>(s_out + ((size_t)cl * IIR_LD + p) * 4));
-      }
-    }
   }
-  if (chain0 + k < g.nchains) carry[(size_t)(chain0 + k) * 4 + c] = v;
-}
-
-// Anticausal half: for e = n-1 .. 0: v = lerp(B[bnd(e-1)], v); OUT[e] = clamp(v). FUSE: OUT is the unsharp mask of
-// `img` against that low-pass value, written in place.
-template <bool ROWS, bool FUSE>
-__global__ __launch_bounds__(64) void k_iir_anticausal(IirImgs im, IirGeom g, size_t npix, float alpha, float amount) {
-  const float* __restrict__ Bf = reinterpret_cast<const float*>(im.buf[blockIdx.y]);
-  const float* __restrict__ carry = Bf + npix * 3;
-  uchar4* __restrict__ out = im.out[blockIdx.y];
-  __shared__ float s_in[IIR_CH * IIR_LD * 4];
-  __shared__ unsigned s_out[IIR_CH * IIR_LD];
-  const int lane = threadIdx.x, k = lane >> 2, c = lane & 3;
-  const int chain0 = blockIdx.x * IIR_CH;
-  const int ntiles = (g.n + IIR_T - 1) / IIR_T;
-  // (native vector type: an array of HIP's float4 structs captured by the lambda is not promoted to registers — it was
-  // 272 bytes of scratch memory per lane, with every prefetched tile waited for at once in order to be stored there)
-  typedef float f4r __attribute__((ext_vector_type(4)));
-  f4r pre[IIR_CH];
-  const int cl = lane & 15, rl = lane >> 4;  // columns: lane = (row of a group of 4, chain), as in k_iir_causal
-  auto load_tile = [&](int t) {  // B at positions bnd(e - 1)
-    if (ROWS) {
-      const int e = min(t * IIR_T + lane, g.n - 1);
-      const int pos = iir_bnd<ROWS>(e - 1, g.n);
-#pragma unroll
-      for (int kk = 0; kk < IIR_CH; ++kk)
-        pre[kk] = iir_get(Bf, iir_px<ROWS>(g, min(chain0 + kk, g.nchains - 1), pos));
-    } else {
-      const int ch = min(chain0 + cl, g.nchains - 1);
-#pragma unroll
-      for (int i = 0; i < IIR_CH; ++i) {
-        const int e = min(t * IIR_T + 4 * i + rl, g.n - 1);
-        pre[i] = iir_get(Bf, (size_t)iir_bnd<ROWS>(e - 1, g.n) * g.w + ch);
-      }
-    }
-  };
-  const float am = 1.0f - alpha;
-  float v = carry[(size_t)min(chain0 + k, g.nchains - 1) * 4 + c];
+  const float b_last = v;  // B[n-1]
+  // ---- backward: tile by tile, the causal values made again from the checkpoint, then the anticausal half over them
   load_tile(ntiles - 1);
+  float ck_next = ck[(size_t)(ntiles - 1) * 64];
   for (int t = ntiles - 1; t >= 0; --t) {
-#pragma unroll
-    for (int kk = 0; kk < IIR_CH; ++kk) {
-      if (ROWS) *reinterpret_cast<f4r*>(s_in + ((size_t)kk * IIR_LD + lane) * 4) = pre[kk];
-      else *reinterpret_cast<f4r*>(s_in + ((size_t)cl * IIR_LD + 4 * kk + rl) * 4) = pre[kk];
-    }
+    const float b_before = ck_next;  // the causal state in front of the tile: B[64 t - 1] (t = 0: X[0])
+    stage_tile();
     S360_WAVE_SYNC();
-    if (t > 0) load_tile(t - 1);
+    if (t > 0) {
+      load_tile(t - 1);
+      ck_next = ck[(size_t)(t - 1) * 64];
+    }
     // FUSE: the image pixels the unsharp mask needs at the end of this tile are requested now (as load-use pairs in the
     // output loop they were 16 serialised round trips per tile)
     unsigned img[IIR_CH];
@@ -1845,22 +1788,27 @@ __global__ __launch_bounds__(64) void k_iir_anticausal(IirImgs im, IirGeom g, si
       }
     }
     const int cnt = min(IIR_T, g.n - t * IIR_T);
-    const float* si = s_in + (size_t)k * IIR_LD * 4 + c;
-    unsigned char* so = reinterpret_cast<unsigned char*>(s_out) + (size_t)k * IIR_LD * 4 + c;
-    int j = cnt - 1;
-    for (; j >= 7; j -= 8) {
-      float ip[8];
+    // B[64 t + j], j = 0..63, in the lane's registers (every index below is a constant after unrolling); the values
+    // behind a ragged tile's end are made from repeated inputs and never read
+    float b[IIR_T];
+    {
+      float u = b_before;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) ip[q] = si[(j - q) * 4] * am;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        v = ip[q] + v * alpha;
-        so[(j - q) * 4] = c == 3 ? (unsigned char)255 : (unsigned char)clamp255(v);
+      for (int j = 0; j < IIR_T; ++j) {
+        u = (float)sb[j * 4] * am + u * alpha;
+        b[j] = u;
       }
     }
-    for (; j >= 0; --j) {
-      v = si[j * 4] * am + v * alpha;
-      so[j * 4] = c == 3 ? (unsigned char)255 : (unsigned char)clamp255(v);
+    // what position 64 t reads, B[bnd(64 t - 1)]: the state in front of the tile, or at the chain's start B[n-1] (rows
+    // wrap) / B[1] (columns reflect)
+    const float b_first = t > 0 ? b_before : ROWS ? b_last : b[1];
+    unsigned char* so = reinterpret_cast<unsigned char*>(s_out) + (size_t)k * IIR_LD * 4 + c;
+#pragma unroll
+    for (int j = IIR_T - 1; j >= 0; --j) {
+      if (j < cnt) {
+        v = (j > 0 ? b[j > 0 ? j - 1 : 0] : b_first) * am + v * alpha;
+        so[j * 4] = c == 3 ? (unsigned char)255 : (unsigned char)clamp255(v);
+      }
     }
     S360_WAVE_SYNC();
 #pragma unroll
@@ -2120,27 +2068,27 @@ void launch_pack_bgr(hipStream_t st, const uchar4* src, int w, int h, uint8_t* d
     hipLaunchKernelGGL(k_pack_bgr, dim3(cdiv(n, 256)), dim3(256), 0, st, src, n, dst);
 }
 // iirLowPass (wrap horizontally, reflect vertically) + sharpenWithIirLowPass on one eye, in place (TRSP:688-696).
-// scratch: w*h float4 + max(w,h) float4 (the chains' carried state).
+// scratch: the chain states at the tile boundaries of one pass, one float per lane, wave and tile (the column pass reuses
+// the row pass's) — about a quarter of a byte per pixel.
 int sharpen_max_images() { return IIR_MAX_IMGS; }
-size_t sharpen_scratch_bytes(int w, int h) { return ((size_t)w * h + (size_t)std::max(w, h)) * sizeof(float4); }
+size_t sharpen_scratch_bytes(int w, int h) {
+  return std::max(iir_waves(h) * iir_tiles(w), iir_waves(w) * iir_tiles(h)) * 64 * sizeof(float);
+}
 // n images of the same size in one set of launches (the chains of one image cannot fill the chip: 16 384 of them for
-// the row pass of a 4096-row eye, each 2 x 8400 dependent steps).
+// the row pass of a 4096-row eye, each 3 x 8400 dependent steps).
 void launch_sharpen_many(hipStream_t st, uchar4* const* imgs, uchar4* const* lps, float* const* scratch, int n, int w,
                          int h, float amount) {
   if (n < 1 || n > IIR_MAX_IMGS) throw std::runtime_error("launch_sharpen_many: 1..32 images per launch");
   const float alpha = powf(0.25f, 1.0f / 4.0f);  // host libm, Filter.h:49
-  const size_t npix = (size_t)w * h;
   const IirGeom gr{w, h, w}, gc{h, w, w};
   IirImgs rows, cols;
   for (int i = 0; i < IIR_MAX_IMGS; ++i) {
     const int k = i < n ? i : 0;
-    rows.x[i] = imgs[k]; rows.out[i] = lps[k]; rows.buf[i] = reinterpret_cast<float4*>(scratch[k]);
-    cols.x[i] = lps[k]; cols.out[i] = imgs[k]; cols.buf[i] = reinterpret_cast<float4*>(scratch[k]);
+    rows.x[i] = imgs[k]; rows.out[i] = lps[k]; rows.ck[i] = scratch[k];
+    cols.x[i] = lps[k]; cols.out[i] = imgs[k]; cols.ck[i] = scratch[k];
   }
-  hipLaunchKernelGGL((k_iir_causal<true>), dim3(cdiv(h, IIR_CH), n), dim3(64), 0, st, rows, gr, npix, alpha);
-  hipLaunchKernelGGL((k_iir_anticausal<true, false>), dim3(cdiv(h, IIR_CH), n), dim3(64), 0, st, rows, gr, npix, alpha, amount);
-  hipLaunchKernelGGL((k_iir_causal<false>), dim3(cdiv(w, IIR_CH), n), dim3(64), 0, st, cols, gc, npix, alpha);
-  hipLaunchKernelGGL((k_iir_anticausal<false, true>), dim3(cdiv(w, IIR_CH), n), dim3(64), 0, st, cols, gc, npix, alpha, amount);
+  hipLaunchKernelGGL((k_iir_pass<true, false>), dim3(cdiv(h, IIR_CH), n), dim3(64), 0, st, rows, gr, alpha, amount);
+  hipLaunchKernelGGL((k_iir_pass<false, true>), dim3(cdiv(w, IIR_CH), n), dim3(64), 0, st, cols, gc, alpha, amount);
 }
 void launch_sharpen(hipStream_t st, uchar4* img, uchar4* lp, float* scratch, int w, int h, float amount) {
   launch_sharpen_many(st, &img, &lp, &scratch, 1, w, h, amount);

@@ -10,14 +10,17 @@ for r in $(seq 1 $R); do
   for v in ${VARIANTS:-old new}; do   # a variant "<lib>:<ENV=value>" runs libs360_<lib>.so with that environment variable
     lib=${v%%:*}; envs=""; [ "$lib" != "$v" ] && envs=${v#*:}
     cp surround360_amd/libs360_$lib.so surround360_amd/libs360.so
-    env $envs timeout 600 python bench.py --full --steps 12 --warmup 6 --no-extras --no-cpu-baseline > $O/${v//[:=]/_}_$r.json 2> $O/${v//[:=]/_}_$r.err
+    # (a run that fails, faults or meets its time limit ends the script: nothing more is started on that GPU)
+    env $envs timeout -k 10 600 python bench.py --full --steps 12 --warmup 6 --no-extras --no-cpu-baseline > $O/${v//[:=]/_}_$r.json 2> $O/${v//[:=]/_}_$r.err \
+      || { rc=$?; echo "$v round $r: bench.py ended with status $rc"; tail -5 $O/${v//[:=]/_}_$r.err; cp $O/libs360_keep.so surround360_amd/libs360.so; exit $rc; }
     python - $O/${v//[:=]/_}_$r.json $v $r <<'P'
 import json, sys
 d = json.load(open(sys.argv[1]))
 k = d["roofline"]["batch_alone_kernel_ms_per_frame"]
-print("%s round %s: value %.2f checked %s  batch alone %.3f ms/frame  median %.3f (in flight %.3f)  sweep %.3f" % (
-    sys.argv[2], sys.argv[3], d["value"], d["checked"], d["roofline"]["batch_alone_ms_per_frame"], k["flow_median"],
-    d["kernel_ms_per_frame_in_flight"]["flow_median"], k["flow_sweep"]))
+print("%s round %s: value %.2f checked %s  HBM %s GB  batch alone %.3f ms/frame  median %.3f (in flight %.3f)  sweep %.3f  finish %.3f (in flight %.3f)" % (
+    sys.argv[2], sys.argv[3], d["value"], d["checked"], d.get("hbm_used_GB_in_timed_region"), d["roofline"]["batch_alone_ms_per_frame"],
+    k["flow_median"], d["kernel_ms_per_frame_in_flight"]["flow_median"], k["flow_sweep"], k["finish"],
+    d["kernel_ms_per_frame_in_flight"]["finish"]))
 P
   done
 done
