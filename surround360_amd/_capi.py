@@ -102,6 +102,8 @@ PNG_DECODE_SYMBOLS = [
 ]
 # ... and the test taps include/s360_debug.h declares (not part of the API)
 DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
+# ... and the one include/s360_debug_final_flow.h declares
+DEBUG_FINAL_FLOW_SYMBOLS = ["s360_debug_upscale_blur"]
 
 _lib = None
 

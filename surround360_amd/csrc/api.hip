@@ -10,6 +10,7 @@
 
 #include "../../include/s360.h"
 #include "../../include/s360_debug.h"
+#include "../../include/s360_debug_final_flow.h"
 #include "ctx.hpp"
 #include "isp.hpp"
 #include "render.hpp"
@@ -495,6 +496,30 @@ int s360_debug_entry_downscale(s360_ctx* c, const uint8_t* src, int sw, int sh, 
     d2h(c, gray_out, gray, B * nd * sizeof(float));
     d2h(c, alpha_out, alpha, B * nd * sizeof(float));
     if (tiled) *tiled = resize_cubic_u8c4_tiled_fits(sw, sh, dw, dh) ? 1 : 0;
+  });
+}
+// test tap: PixFlow's final upscale + scalar + 3x3 blur alone on caller-made flows of any size
+int s360_debug_upscale_blur(s360_ctx* c, const float* src, int sw, int sh, int batch, int dw, int dh, float post_scale, int generic,
+                            float* out, int* tiled) {
+  return guard(c, [&] {
+    need(c && src && out, "null argument");
+    need(sw > 0 && sh > 0 && dw > 0 && dh > 0 && batch >= 1 && batch <= kMaxFlows, "bad size");
+    const size_t ns = (size_t)sw * sh, nd = (size_t)dw * dh, B = batch;
+    c->op_a.ensure(B * ns * sizeof(float2));
+    c->op_d.ensure(B * sizeof(void*));
+    h2d(c, c->op_a.p, src, B * ns * sizeof(float2));
+    // as FlowEngine::compute launches it: the destinations through a table of pointers, here one allocation per flow
+    std::vector<DevBuf> outs(B);
+    std::vector<float*> tab(B);  // (lives until the downloads below have synchronised the stream)
+    for (size_t b = 0; b < B; ++b) {
+      outs[b].ensure(nd * sizeof(float2));
+      tab[b] = outs[b].as<float>();
+    }
+    h2d(c, c->op_d.p, tab.data(), B * sizeof(void*));
+    launch_upscale_blur(c->st, c->op_a.as<float2>(), sw, sh, ns, nullptr, dw, dh, nd, batch, post_scale, gaussian_taps(3, 1.0f),
+                        c->op_d.as<float*>(), generic != 0);
+    for (size_t b = 0; b < B; ++b) d2h(c, out + 2 * nd * b, outs[b].p, nd * sizeof(float2));
+    if (tiled) *tiled = (!generic && upscale_blur_tiled_fits(sw, sh, dw, dh)) ? 1 : 0;
   });
 }
 

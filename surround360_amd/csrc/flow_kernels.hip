@@ -748,6 +748,165 @@ __global__ __launch_bounds__(NT) void k_sepblur(const float* __restrict__ src, f
 }
 
 // ------------------------------------------------------------------------------------------
+// The final flow of PixFlow.h:175-182 — resize(flow, originalSize, INTER_LINEAR), flow *= s, GaussianBlur 3x3 — for scales around
+// 2 in both directions (607x884 -> 1214x1769 side flows, 5040x1052 -> 10080x2104 pole flows): k_sepblur<1, 2, 0, 2>'s results
+// bit for bit, one workgroup per 64x16 output tile. There every one of the 66x18 elements of the blur's input tile forms its two
+// source coordinates in double precision and does four scattered 8-byte loads and a whole bilinear evaluation, and the
+// horizontal interpolation of a source row is evaluated once per OUTPUT row that uses it (3.3 times): 0.25 of HBM. Here
+//   1. 84 threads compute the resize_coord (double, as there) and the border rules of the tile's 66 columns and 18 rows once;
+//   2. the source box — min .. max + 1 over those columns and rows: near the border the reflected ones are not monotone, but the
+//      smallest and the largest destination coordinate are among the first two and the last two — is loaded with coalesced row
+//      loads, all requested before the first LDS store;
+//   3. the horizontal pass S[sx] * a0 + S[sx + 1] * a1 runs once per (source row, destination column),
+//   4. the vertical pass h0 * b0 + h1 * b1, then *= post_scale, once per tile element, into the blur's input tile;
+//   5. the 3x3 row and column passes are k_sepblur's.
+// The same float operations in the same order (-ffp-contract=off), evaluated less often. Columns and rows of the input tile that
+// only feed outputs outside the image repeat the last one that is needed (k_sepblur reflects on: values nobody stores), so that
+// the box is that of at most 66 x 18 consecutive destination positions: the launcher checks UB_BW x UB_BH from the two scales.
+// LDS: exactly k_sepblur<1, 2, 0, 2>'s two tiles (19008 bytes) — the box lives in the input tile's storage until the vertical
+// pass writes it, the horizontal-pass buffer and the coordinate tables in the row-pass result's until the row pass does.
+constexpr int UB_TW = 64, UB_TH = 16, UB_IW = UB_TW + 2, UB_IH = UB_TH + 2, UB_IWP = UB_IW | 1, UB_BW = 40, UB_BH = 14;
+constexpr int UB_IN_FLOATS = UB_IH * UB_IWP * 2, UB_MID_FLOATS = UB_IH * (UB_TW + 1) * 2, UB_H_FLOATS = UB_BH * UB_IW * 2;
+static_assert(UB_BH * UB_BW * 2 <= UB_IN_FLOATS, "the source box shares the input tile's storage");
+static_assert(UB_H_FLOATS + 2 * UB_IW + 3 * UB_IH <= UB_MID_FLOATS, "horizontal pass + tables share the row-pass result's storage");
+bool upscale_blur_tiled_fits(int sw, int sh, int dw, int dh) {
+  const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
+  // an upscale by at most 2.5 (the kernel is laid out and measured for 2), and from below whatever the box holds: the
+  // first taps of the first and the last of n consecutive positions lie at most ceil((n - 1) * scale) + 1 apart (+ 1: the
+  // coordinate is rounded to float before its floor is taken), the last one's second tap 1 further
+  return 2 * (long long)dw <= 5 * (long long)sw && 2 * (long long)dh <= 5 * (long long)sh && (int)std::ceil((UB_IW - 1) * scx) + 3 <= UB_BW && (int)std::ceil((UB_IH - 1) * scy) + 3 <= UB_BH;
+}
+__global__ __launch_bounds__(256) void k_upscale_blur_tiled(const float2* __restrict__ src, float* __restrict__ dst, int w, int h,
+                                                            size_t bs, BlurTaps taps, float* const* __restrict__ dst_tab,
+                                                            UpSrc up) {
+  __shared__ __attribute__((aligned(16))) float s_raw[UB_IN_FLOATS + UB_MID_FLOATS];
+  float2(*s_in)[UB_IWP] = reinterpret_cast<float2(*)[UB_IWP]>(s_raw);
+  float2(*s_mid)[UB_TW + 1] = reinterpret_cast<float2(*)[UB_TW + 1]>(s_raw + UB_IN_FLOATS);
+  float2(*s_box)[UB_BW] = reinterpret_cast<float2(*)[UB_BW]>(s_raw);
+  float2(*s_h)[UB_IW] = reinterpret_cast<float2(*)[UB_IW]>(s_raw + UB_IN_FLOATS);
+  int* s_sx = reinterpret_cast<int*>(s_raw + UB_IN_FLOATS + UB_H_FLOATS);  // per tile column: first tap (border rules applied)
+  float* s_fx = reinterpret_cast<float*>(s_sx + UB_IW);                     // ... and its fraction
+  int* s_r0 = s_sx + 2 * UB_IW;                                             // per tile row: the two clipped source rows
+  int* s_r1 = s_r0 + UB_IH;
+  float* s_fy = reinterpret_cast<float*>(s_r1 + UB_IH);
+  const int tid = threadIdx.x;
+  const TileId tile = xcd_tile();
+  const int tx0 = tile.x * UB_TW, ty0 = tile.y * UB_TH;
+  const int nvx = min(UB_TW, w - tx0), nvy = min(UB_TH, h - ty0);  // outputs of this tile inside the image (>= 1)
+  src += up.sbs * tile.z;
+  // 1. coordinates and weights: tile column lx is destination column reflect101(tx0 - 1 + lx), needed up to lx = nvx + 1
+  if (tid < UB_IW) {
+    int sx;
+    float fx;
+    resize_coord(reflect101(tx0 - 1 + min(tid, nvx + 1), w), up.scx, &sx, &fx);
+    if (sx < 0) { fx = 0; sx = 0; }
+    if (sx >= up.sw - 1) { fx = 0; sx = up.sw - 1; }
+    s_sx[tid] = sx;
+    s_fx[tid] = fx;
+  } else if (tid >= 128 && tid < 128 + UB_IH) {  // (another wave)
+    const int ly = tid - 128;
+    int sy;
+    float fy;
+    resize_coord(reflect101(ty0 - 1 + min(ly, nvy + 1), h), up.scy, &sy, &fy);
+    s_r0[ly] = clip_idx(sy, up.sh);
+    s_r1[ly] = clip_idx(sy + 1, up.sh);
+    s_fy[ly] = fy;
+  }
+  __syncthreads();
+  // 2. the box: source columns bx0 .. bx1 (the second tap of a column at the right border is not read), rows by0 .. by1
+  const int bx0 = min(s_sx[0], s_sx[1]), by0 = min(s_r0[0], s_r0[1]);
+  const int bx1 = min(max(s_sx[nvx], s_sx[nvx + 1]) + 1, up.sw - 1), by1 = max(s_r1[nvy], s_r1[nvy + 1]);
+  const int nbw = clip_idx(bx1 - bx0, UB_BW) + 1, nbh = clip_idx(by1 - by0, UB_BH) + 1;  // (never cut: launcher)
+  {
+    constexpr int kIters = (UB_BW * UB_BH + 255) / 256;
+    float2 ld[kIters];
+    // all elements requested before the first is stored (indices clamped, no early-out: see k_sepblur)
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int i = tid + it * 256;
+      const int r = min(i / UB_BW, nbh - 1), c = min(i % UB_BW, nbw - 1);
+      ld[it] = src[(size_t)min(by0 + r, up.sh - 1) * up.sw + min(bx0 + c, up.sw - 1)];
+    }
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int i = tid + it * 256;
+      const int r = i / UB_BW, c = i % UB_BW;
+      if (r < nbh && c < nbw) s_box[r][c] = ld[it];
+    }
+  }
+  __syncthreads();
+  // 3. horizontal pass: once per (box row, tile column)
+  for (int t = tid; t < nbh * UB_IW; t += 256) {
+    const int r = t / UB_IW, c = t - r * UB_IW;
+    const int sx = s_sx[c], cx = clip_idx(sx - bx0, UB_BW);
+    const float2 p0 = s_box[r][cx];
+    float2 hv;
+    if (sx >= up.sw - 1) {
+      hv.x = p0.x * 1.0f;
+      hv.y = p0.y * 1.0f;
+    } else {
+      const float fx = s_fx[c];
+      const float a0 = 1.f - fx, a1 = fx;
+      const float2 p1 = s_box[r][min(cx + 1, UB_BW - 1)];
+      hv.x = p0.x * a0 + p1.x * a1;
+      hv.y = p0.y * a0 + p1.y * a1;
+    }
+    s_h[r][c] = hv;
+  }
+  __syncthreads();
+  // 4. vertical pass and the scalar multiply: once per element of the blur's input tile
+  for (int t = tid; t < UB_IH * UB_IW; t += 256) {
+    const int ly = t / UB_IW, lx = t - ly * UB_IW;
+    const float fy = s_fy[ly];
+    const float b0 = 1.f - fy, b1 = fy;
+    const float2 h0 = s_h[clip_idx(s_r0[ly] - by0, UB_BH)][lx], h1 = s_h[clip_idx(s_r1[ly] - by0, UB_BH)][lx];
+    float vx = h0.x * b0 + h1.x * b1, vy = h0.y * b0 + h1.y * b1;
+    vx *= up.post_scale;
+    vy *= up.post_scale;
+    s_in[ly][lx] = make_float2(vx, vy);
+  }
+  __syncthreads();
+  // 5. k_sepblur<1, 2, 0, *>'s row pass (SymmRowSmallFilter) ...
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  for (int t = tid; t < UB_IH * (UB_TW / 4); t += 256) {
+    const int ly = t % UB_IH, lx0 = (t / UB_IH) * 4;
+    float2 v[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] = s_in[ly][lx0 + j];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      float2 acc;
+      acc.x = taps.k[0] * v[o + 1].x;
+      acc.x += taps.k[1] * (v[o + 2].x + v[o].x);
+      acc.y = taps.k[0] * v[o + 1].y;
+      acc.y += taps.k[1] * (v[o + 2].y + v[o].y);
+      s_mid[ly][lx0 + o] = acc;
+    }
+  }
+  __syncthreads();
+  // ... and its column pass (SymmColumnFilter: centre + delta (= +0), then the symmetric pair)
+  dst = dst_tab ? dst_tab[tile.z] : dst + bs * 2 * tile.z;
+  {
+    const int lx = tid % UB_TW, ly0 = (tid / UB_TW) * 4, gx = tx0 + lx;
+    f32x2 p[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const float2 q = s_mid[ly0 + j][lx];
+      p[j] = f32x2{q.x, q.y};
+    }
+    if (gx >= w) return;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      const int gy = ty0 + ly0 + o;
+      if (gy >= h) continue;
+      f32x2 acc = taps.k[0] * p[o + 1] + 0.0f;
+      acc += taps.k[1] * (p[o + 2] + p[o]);
+      *reinterpret_cast<float2*>(dst + ((size_t)gy * w + gx) * 2) = make_float2(acc.x, acc.y);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // resize INTER_LINEAR float (pyramid x0.9, PixFlow.h:487; final upscale :176).
 // Horizontal: s<0 => (0, f=0); s>=sw-1 => S[sw-1]*1; vertical rows clipped, f kept.
 template <int CN, int PPT>
@@ -1217,8 +1376,10 @@ void launch_diffusion_adjust(hipStream_t st, const float2* flow, float2* dst, in
   launch_sepblur_t<7, 2, 4, 0>(st, (const float*)flow, (float*)dst, w, h, bs, B, t, A, idx, prev, const_cast<float*>(motion), nullptr, up);
 }
 // resize(flow, originalSize, INTER_LINEAR); flow *= s; GaussianBlur(flow, 3x3) in one pass (PixFlow.h:175-182)
+// (the tiled kernel where a tile's source box fits — upscale_blur_tiled_fits — and `generic` is not set; k_sepblur<1, 2, 0, 2>
+// otherwise)
 void launch_upscale_blur(hipStream_t st, const float2* src, int sw, int sh, size_t sbs, float2* dst, int dw, int dh,
-                         size_t dbs, int B, float post_scale, const BlurTaps& t, float* const* dst_tab) {
+                         size_t dbs, int B, float post_scale, const BlurTaps& t, float* const* dst_tab, bool generic) {
   static const FlowIdx none = {nullptr, nullptr};
   if (t.r != 1) throw std::runtime_error("launch_upscale_blur: 3x3 kernel expected");
   UpSrc up;
@@ -1226,7 +1387,11 @@ void launch_upscale_blur(hipStream_t st, const float2* src, int sw, int sh, size
   up.scx = 1.0 / ((double)dw / (double)sw);
   up.scy = 1.0 / ((double)dh / (double)sh);
   up.post_scale = post_scale;
-  launch_sepblur_t<1, 2, 0, 2>(st, (const float*)src, (float*)dst, dw, dh, dbs, B, t, nullptr, none, nullptr, nullptr, dst_tab, up);
+  if (!generic && upscale_blur_tiled_fits(sw, sh, dw, dh))
+    hipLaunchKernelGGL(k_upscale_blur_tiled, dim3((dw + UB_TW - 1) / UB_TW, (dh + UB_TH - 1) / UB_TH, B), dim3(256), 0, st, src,
+                       (float*)dst, dw, dh, dbs, t, dst_tab, up);
+  else
+    launch_sepblur_t<1, 2, 0, 2>(st, (const float*)src, (float*)dst, dw, dh, dbs, B, t, nullptr, none, nullptr, nullptr, dst_tab, up);
 }
 // Sobel + 3x3 Gaussian of a float plane in one pass -> packed (Ix, Iy) (PixFlow.h:353-366)
 void launch_gradients(hipStream_t st, const float* I, float2* G, int w, int h, size_t bs, int B, const BlurTaps& t) {

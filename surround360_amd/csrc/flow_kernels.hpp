@@ -58,8 +58,13 @@ void launch_diffusion(hipStream_t st, const float2* flow, float2* dst, int w, in
                       const BlurTaps& t, const float* A, const FlowIdx& idx);
 void launch_diffusion_adjust(hipStream_t st, const float2* flow, float2* dst, int w, int h, size_t bs, int B, const BlurTaps& t,
                              const float* A, const FlowIdx& idx, const float2* prev, const float* motion, float prev_scale);
+// resize INTER_LINEAR + scalar multiply + 3x3 blur (PixFlow.h:175-182). Scales around 2 whose 64x16 tiles' source boxes fit
+// (upscale_blur_tiled_fits) take k_upscale_blur_tiled, everything else — and everything with `generic` — k_sepblur<1, 2, 0, 2>:
+// same results bit for bit.
+bool upscale_blur_tiled_fits(int sw, int sh, int dw, int dh);
 void launch_upscale_blur(hipStream_t st, const float2* src, int sw, int sh, size_t sbs, float2* dst, int dw, int dh,
-                         size_t dbs, int B, float post_scale, const BlurTaps& t, float* const* dst_tab = nullptr);
+                         size_t dbs, int B, float post_scale, const BlurTaps& t, float* const* dst_tab = nullptr,
+                         bool generic = false);
 void launch_gradients(hipStream_t st, const float* I, float2* G, int w, int h, size_t bs, int B, const BlurTaps& t);
 // G == nullptr: half-records (float2, throughput sweep kernel); G given: full records (float4, latency sweep kernel)
 void launch_blur_to_records(hipStream_t st, const float2* flow, void* rec, int w, int h, size_t bs, int B,

@@ -665,8 +665,16 @@ void dev_feather_alpha_to_ext(s360_ctx* c, const uchar4* pano, int cols, int row
   }
 }
 
+bool composite_fused_enabled() {
+  static const bool on = [] {
+    const char* e = std::getenv("S360_COMPOSITE_FUSED");
+    return !(e && e[0] == '0' && e[1] == 0);
+  }();
+  return on;
+}
+
 void dev_pole_unit_post(s360_ctx* c, const uchar4* extFisheye, const float2* flow, int cols, int rows, int extW,
-                        uchar4* warped_out, int eqrH) {
+                        uchar4* warped_out, int eqrH, bool pad_rows) {
   FrameState& F = frame_state(c);
   PoleWarpParams pw;
   pw.cols = cols; pw.rows = rows; pw.extW = extW;
@@ -682,7 +690,7 @@ void dev_pole_unit_post(s360_ctx* c, const uchar4* extFisheye, const float2* flo
   F.sc->warpTiles.ensure(remap_packed_tiles(extW, rows) * 16);
   launch_pole_warp_packed(c->st, extFisheye, flow, F.sc->warpedExt.as<uchar4>(), pw, F.tab.dev, F.sc->warpPacked.as<unsigned>(),
                           F.sc->warpTiles.p);
-  launch_pole_finish(c->st, F.sc->warpedExt.as<uchar4>(), warped_out, eqrH, pw);
+  launch_pole_finish(c->st, F.sc->warpedExt.as<uchar4>(), warped_out, pad_rows ? eqrH : std::min(rows, eqrH), pw);
 }
 
 namespace {
@@ -874,9 +882,20 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
         ProfScope ps(prof, "pole_warp");
         for (int u = 0; u < 4; ++u)
           if (pole_mask & (1 << u)) {
-            F.sc->poleWarped[u].ensure(en * sizeof(uchar4));
+            // the layer's own rows are written every frame, the transparent rows below them once: when the buffer is new
+            // (DevBuf::ensure does not zero) or its layout changed. Nothing on the frame path writes them afterwards
+            // (frame_gather_pole_layers zeroes them itself for the layers it receives)
+            SlotScratch& S = *F.sc;
+            S.poleWarped[u].ensure(en * sizeof(uchar4));
+            const size_t padFrom = (size_t)W * std::min(rowsOf(u), H) * sizeof(uchar4), padTo = en * sizeof(uchar4);
+            if (S.polePadBuf[u] != S.poleWarped[u].p || S.polePadFrom[u] != padFrom || S.polePadTo[u] != padTo) {
+              if (padTo > padFrom) S360_HIP(hipMemsetAsync(S.poleWarped[u].as<uint8_t>() + padFrom, 0, padTo - padFrom, st));
+              S.polePadBuf[u] = S.poleWarped[u].p;
+              S.polePadFrom[u] = padFrom;
+              S.polePadTo[u] = padTo;
+            }
             dev_pole_unit_post(c, ext + (u < 2 ? 4 : 5) * xs, F.poleFlows.as<float2>() + u * xs, W, rowsOf(u), extW,
-                               F.sc->poleWarped[u].as<uchar4>(), H);
+                               S.poleWarped[u].as<uchar4>(), H, false);
             F.poleFrame[u] = F.frames_done;
             F.sc->poleOwner[u] = &F;
           }
@@ -897,6 +916,16 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
         if ((composite_mask & (1 << u)) && (!F.sc->poleWarped[u].p || F.poleFrame[u] != F.frames_done || F.sc->poleOwner[u] != &F))  // (an earlier frame's, or another slot's, layer is not this frame's)
           throw Error(S360_ERR_STATE, "composite: the warped layer of pole unit " + std::to_string(u) + " of this frame is neither computed nor received");
       for (int e = 0; e < 2; ++e) {
+        const uchar4* top = (composite_mask & (1 << e)) ? F.sc->poleWarped[e].as<uchar4>() : nullptr;
+        const uchar4* bot = (composite_mask & (4 << e)) ? F.sc->poleWarped[2 + e].as<uchar4>() : nullptr;
+        if (!top && !bot) continue;
+        // both layers in one pass over the eye (widths that are no multiple of 4 keep the launch per layer)
+        if (composite_fused_enabled() && composite_poles_fits(F.pano[e].as<uchar4>(), top, bot, F.sc->panoTmp.as<uchar4>(), W)) {
+          launch_composite_poles(st, F.pano[e].as<uchar4>(), top, rowsT, bot, rowsB, F.sc->panoTmp.as<uchar4>(), W, H, F.tab.dev);
+          std::swap(F.pano[e].p, F.sc->panoTmp.p);
+          std::swap(F.pano[e].cap, F.sc->panoTmp.cap);
+          continue;
+        }
         if (composite_mask & (1 << e)) {
           launch_flatten(st, F.pano[e].as<uchar4>(), F.sc->poleWarped[e].as<uchar4>(), F.sc->panoTmp.as<uchar4>(), W, H, 0,
                          F.tab.dev);

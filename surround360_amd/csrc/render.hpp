@@ -34,6 +34,10 @@ struct SlotScratch {
   DevBuf panoFlip[2], panoTmp;
   DevBuf topSph, botSph;
   DevBuf warpedExt, poleWarped[4];
+  // poleWarped[u] is a whole eye (W x H) of which the frame path writes only the layer's own rows: [polePadFrom[u], polePadTo[u])
+  // are the bytes behind them that were zeroed (transparent padding) when the buffer was allocated or its layout last changed
+  const void* polePadBuf[4] = {nullptr, nullptr, nullptr, nullptr};
+  size_t polePadFrom[4] = {0, 0, 0, 0}, polePadTo[4] = {0, 0, 0, 0};
   const void* poleOwner[4] = {nullptr, nullptr, nullptr, nullptr};  // the slot (FrameState) whose frame poleWarped[u] holds: with the
                                                                     // split phases two slots could interleave (frame_composite checks)
   DevBuf warpPacked, warpTiles;  // this frame's pole warp as packed coordinates + tile boxes (launch_pole_warp_packed)
@@ -160,8 +164,12 @@ void comm_loopback(s360_ctx* c, int src_pair, int dst_pair);
 void dev_feather_alpha_to_ext(s360_ctx* c, const uchar4* pano_top_rows, int cols, int rows, uchar4* ext, int extW,
                               int erode_size = -1, const int* taps = nullptr);
 std::vector<int> feather_gauss_taps(int erode_size);
+// pad_rows: the rows of warped_out below the layer's own are written too (transparent black); the frame path keeps them zeroed itself
 void dev_pole_unit_post(s360_ctx* c, const uchar4* extFisheye, const float2* flow, int cols, int rows, int extW,
-                        uchar4* warped_out /*cols x eqrH*/, int eqrH);
+                        uchar4* warped_out /*cols x eqrH*/, int eqrH, bool pad_rows = true);
+// S360_COMPOSITE_FUSED=0: the pole layers are composited one k_flatten launch each, as before k_composite_poles_v4 (A/B runs
+// and tests; results do not depend on it). Read once per process.
+bool composite_fused_enabled();
 
 // api.hip: does [p, p + bytes) lie in a buffer from s360_host_alloc (page-locked: uploads need no staging copy)?
 bool host_is_pinned(const void* p, size_t bytes);

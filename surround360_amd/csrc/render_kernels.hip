@@ -1379,6 +1379,40 @@ __global__ __launch_bounds__(256) void k_flatten_v4(const uint4* __restrict__ ba
   out[(size_t)y * w4 + x4] = o;
 }
 
+// Both pole layers of an eye in one pass (TRSP:864-885: flatten the top layer onto the panorama, then the bottom layer onto
+// that). A layer holds its pole's rows (top_rows / bottom_rows of h, first in the layer; the bottom layer is read mirrored,
+// as k_flatten_v4's flip_top reads it); below them it is transparent black. A row outside a layer's own rows is not loaded:
+// its pixel is t = 0, and goes through flatten_px like any other (flatten_px(b, 0) is not b: softmaxL[0] < 1 and the deghost
+// coefficient against black is large). A null layer is absent and skipped, which is not the same. One load of the base,
+// at most one of each layer, one 16-byte store: as two k_flatten_v4 launches the panorama made two round trips and the
+// layers' padding one.
+__device__ __forceinline__ uint4 flatten_px4(uint4 b, uint4 t, const DevTables& T) {
+  uint4 o;
+  o.x = __builtin_bit_cast(unsigned, flatten_px(__builtin_bit_cast(uchar4, b.x), __builtin_bit_cast(uchar4, t.x), T));
+  o.y = __builtin_bit_cast(unsigned, flatten_px(__builtin_bit_cast(uchar4, b.y), __builtin_bit_cast(uchar4, t.y), T));
+  o.z = __builtin_bit_cast(unsigned, flatten_px(__builtin_bit_cast(uchar4, b.z), __builtin_bit_cast(uchar4, t.z), T));
+  o.w = __builtin_bit_cast(unsigned, flatten_px(__builtin_bit_cast(uchar4, b.w), __builtin_bit_cast(uchar4, t.w), T));
+  return o;
+}
+__global__ __launch_bounds__(256) void k_composite_poles_v4(const uint4* __restrict__ base, const uint4* __restrict__ top,
+                                                            const uint4* __restrict__ bottom, uint4* __restrict__ out, int w4,
+                                                            int h, int top_rows, int bottom_rows, DevTables T) {
+  const int x4 = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x4 >= w4) return;
+  const int yb = h - 1 - y;
+  // (the loads first, then the arithmetic: the second flatten depends on the first, its layer's load does not)
+  uint4 b = base[(size_t)y * w4 + x4];
+  uint4 t = make_uint4(0u, 0u, 0u, 0u), u = make_uint4(0u, 0u, 0u, 0u);
+  if (top && y < top_rows) t = top[(size_t)y * w4 + x4];
+  if (bottom && yb < bottom_rows) {
+    const uint4 r = bottom[(size_t)yb * w4 + (w4 - 1 - x4)];
+    u = make_uint4(r.w, r.z, r.y, r.x);
+  }
+  if (top) b = flatten_px4(b, t, T);
+  if (bottom) b = flatten_px4(b, u, T);
+  out[(size_t)y * w4 + x4] = b;
+}
+
 // ---- cubemap output (ImageWarper.cpp:95-141 + CvUtil.cpp:117-138) ------------------------------------------------
 // One thread per pixel of the stacked stereo cubemap: picks (eye, face, i, j) from the output position (faces are
 // flipped horizontally in the "video" layout), reads the cached face warp map and does remap INTER_CUBIC /
@@ -1990,13 +2024,26 @@ void launch_pole_warp_packed(hipStream_t st, const uchar4* extFisheye, const flo
                      dim3(PT_W, PT_TY), 0, st, extFisheye, pw.extW, pw.rows, packed, reinterpret_cast<const int4*>(tiles), mf,
                      warpedExt, pw.extW, pw.rows, T.bicubic_i, 0, 1, (size_t)0, (size_t)0, nt, T.bicubic_w1, T.bicubic_res);
 }
-void launch_pole_finish(hipStream_t st, const uchar4* warpedExt, uchar4* out, int eqrH, const PoleWarpParams& pw) {
+// out_rows: the rows of `out` that are written, pw.rows (the layer's own) .. the eye's height (those below the layer's own
+// are stored as transparent black)
+void launch_pole_finish(hipStream_t st, const uchar4* warpedExt, uchar4* out, int out_rows, const PoleWarpParams& pw) {
   if ((pw.cols & 3) == 0 && (pw.extW & 3) == 0 && pw.cols + ((pw.maxBlendX + 3) & ~3) <= pw.extW &&
       (reinterpret_cast<uintptr_t>(warpedExt) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0)
-    hipLaunchKernelGGL(k_pole_finish_v4, dim3(cdiv(pw.cols / 4, 256), eqrH), dim3(256), 0, st,
-                       reinterpret_cast<const uint4*>(warpedExt), reinterpret_cast<uint4*>(out), eqrH, pw);
+    hipLaunchKernelGGL(k_pole_finish_v4, dim3(cdiv(pw.cols / 4, 256), out_rows), dim3(256), 0, st,
+                       reinterpret_cast<const uint4*>(warpedExt), reinterpret_cast<uint4*>(out), out_rows, pw);
   else
-    hipLaunchKernelGGL(k_pole_finish, dim3(cdiv(pw.cols, 256), eqrH), dim3(256), 0, st, warpedExt, out, eqrH, pw);
+    hipLaunchKernelGGL(k_pole_finish, dim3(cdiv(pw.cols, 256), out_rows), dim3(256), 0, st, warpedExt, out, out_rows, pw);
+}
+bool composite_poles_fits(const uchar4* base, const uchar4* top, const uchar4* bottom, const uchar4* out, int w) {
+  return (w & 3) == 0 && ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(top) |
+                           reinterpret_cast<uintptr_t>(bottom) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+}
+void launch_composite_poles(hipStream_t st, const uchar4* base, const uchar4* top, int top_rows, const uchar4* bottom,
+                            int bottom_rows, uchar4* out, int w, int h, const DevTables& T) {
+  if (!composite_poles_fits(base, top, bottom, out, w)) throw std::runtime_error("launch_composite_poles: width or alignment");
+  hipLaunchKernelGGL(k_composite_poles_v4, dim3(cdiv(w / 4, 256), h), dim3(256), 0, st, reinterpret_cast<const uint4*>(base),
+                     reinterpret_cast<const uint4*>(top), reinterpret_cast<const uint4*>(bottom), reinterpret_cast<uint4*>(out),
+                     w / 4, h, std::min(top_rows, h), std::min(bottom_rows, h), T);
 }
 void launch_flatten(hipStream_t st, const uchar4* base, const uchar4* top, uchar4* out, int w, int h, int flip_top,
                     const DevTables& T) {

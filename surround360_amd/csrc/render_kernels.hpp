@@ -87,11 +87,18 @@ void launch_extend_wrap(hipStream_t st, const uchar4* img, const uint8_t* alpha 
 void launch_pole_warp_packed(hipStream_t st, const uchar4* extFisheye, const float2* flow, uchar4* warpedExt,
                              const PoleWarpParams& pw, const DevTables& T, unsigned* packed /* extW*rows */,
                              void* tiles /* remap_packed_tiles(extW, rows) * 16 bytes */);
-// seam blend + alpha ramp + bottom padding (TRSP:505-546): out is eqrW x eqrH
-void launch_pole_finish(hipStream_t st, const uchar4* warpedExt, uchar4* out, int eqrH, const PoleWarpParams& pw);
+// seam blend + alpha ramp + bottom padding (TRSP:505-546): out is eqrW x eqrH, of which rows 0 .. out_rows - 1 are written
+// (pw.rows: the layer's own rows only, the padding is the caller's; eqrH: the padding too)
+void launch_pole_finish(hipStream_t st, const uchar4* warpedExt, uchar4* out, int out_rows, const PoleWarpParams& pw);
 // flattenLayersDeghostPreferBase (CvUtil.cpp:224-260); flip_top: top layer is indexed (W-1-x, H-1-y)
 void launch_flatten(hipStream_t st, const uchar4* base, const uchar4* top, uchar4* out, int w, int h, int flip_top,
                     const DevTables& T);
+// launch_flatten(top, flip_top = 0) followed by launch_flatten(bottom, flip_top = 1) in one pass over the eye: the layers hold
+// top_rows / bottom_rows rows (first in the layer) and count as transparent black below them without being read there; a null
+// layer is absent. Needs composite_poles_fits (w % 4 == 0, 16-byte aligned buffers).
+bool composite_poles_fits(const uchar4* base, const uchar4* top, const uchar4* bottom, const uchar4* out, int w);
+void launch_composite_poles(hipStream_t st, const uchar4* base, const uchar4* top, int top_rows, const uchar4* bottom,
+                            int bottom_rows, uchar4* out, int w, int h, const DevTables& T);
 // BGRA rows -> packed BGR at row offset (stackVertical + BGRA2BGR, TRSP:890-894, 960)
 // stereo cubemap from the two eye panoramas through cached face warp maps (TRSP:917-935)
 void launch_cubemap(hipStream_t st, const uchar4* eyeL, const uchar4* eyeR, int sw, int sh, const float2* maps, int fw,

@@ -180,6 +180,16 @@ class Context:
                                                   _p(alpha), C.byref(tiled)))
         return down, gray, alpha, bool(tiled.value)
 
+    def debug_upscale_blur(self, src_flow, dw, dh, post_scale, generic=False):
+        """PixFlow's final step on a stack of flows (b x sh x sw x 2): (resized, scaled and blurred flows, tiled kernel taken)."""
+        src = np.ascontiguousarray(src_flow, np.float32)
+        b, sh, sw = src.shape[:3]
+        out = np.empty((b, dh, dw, 2), np.float32)
+        tiled = C.c_int()
+        self._ck(lib().s360_debug_upscale_blur(self.h, _p(src), sw, sh, b, dw, dh, C.c_float(post_scale), 1 if generic else 0,
+                                               _p(out), C.byref(tiled)))
+        return out, bool(tiled.value)
+
     def spherical_warp_map(self, cam, dw, dh, l, r, t, b):
         m = np.empty((dh, dw, 2), np.float32)
         self._ck(lib().s360_spherical_warp_map(self.h, _p(m), dw, dh, C.byref(cam), C.c_float(l), C.c_float(r),

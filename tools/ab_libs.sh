@@ -17,10 +17,12 @@ for r in $(seq 1 $R); do
 import json, sys
 d = json.load(open(sys.argv[1]))
 k = d["roofline"]["batch_alone_kernel_ms_per_frame"]
-print("%s round %s: value %.2f checked %s  HBM %s GB  batch alone %.3f ms/frame  median %.3f (in flight %.3f)  sweep %.3f  finish %.3f (in flight %.3f)" % (
+f = d["kernel_ms_per_frame_in_flight"]
+print("%s round %s: value %.2f checked %s  HBM %s GB  batch alone %.3f ms/frame  median %.3f (in flight %.3f)  sweep %.3f  finish %.3f (in flight %.3f)"
+      "  flow_final %.3f (in flight %.3f)  flatten %.3f (in flight %.3f)  pole_warp %.3f (in flight %.3f)" % (
     sys.argv[2], sys.argv[3], d["value"], d["checked"], d.get("hbm_used_GB_in_timed_region"), d["roofline"]["batch_alone_ms_per_frame"],
-    k["flow_median"], d["kernel_ms_per_frame_in_flight"]["flow_median"], k["flow_sweep"], k["finish"],
-    d["kernel_ms_per_frame_in_flight"]["finish"]))
+    k["flow_median"], f["flow_median"], k["flow_sweep"], k["finish"], f["finish"],
+    k["flow_final"], f["flow_final"], k["flatten"], f["flatten"], k["pole_warp"], f["pole_warp"]))
 P
   done
 done

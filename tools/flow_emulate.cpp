@@ -98,6 +98,26 @@ extern "C" int emu_entry_downscale(const uint8_t* src, int sw, int sh, int B, in
     return -1;
   }
 }
+// The final flow (INTER_LINEAR resize of B flows sw x sh to dw x dh, * post_scale, 3x3 Gaussian blur), written through a table of
+// B destination pointers as FlowEngine does. Returns 1 when the tiled kernel took the shape, 0 when k_sepblur<1, 2, 0, 2> did.
+static int emu_upscale_blur_impl(const float* src, int sw, int sh, int B, int dw, int dh, float post_scale, float* out, bool generic) {
+  try {
+    const size_t ns = (size_t)sw * sh, nd = (size_t)dw * dh;
+    std::vector<float*> tab(B);
+    for (int b = 0; b < B; ++b) tab[b] = out + 2 * nd * b;
+    launch_upscale_blur(nullptr, (const float2*)src, sw, sh, ns, nullptr, dw, dh, nd, B, post_scale, gaussian_taps(3, 1.0f), tab.data(),
+                        generic);
+    return !generic && upscale_blur_tiled_fits(sw, sh, dw, dh) ? 1 : 0;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+extern "C" int emu_upscale_blur(const float* src, int sw, int sh, int B, int dw, int dh, float post_scale, float* out) {
+  return emu_upscale_blur_impl(src, sw, sh, B, dw, dh, post_scale, out, false);
+}
+extern "C" int emu_upscale_blur_generic(const float* src, int sw, int sh, int B, int dw, int dh, float post_scale, float* out) {
+  return emu_upscale_blur_impl(src, sw, sh, B, dw, dh, post_scale, out, true);
+}
 // k_gray_alpha on B images of n pixels.
 extern "C" int emu_gray_alpha(const uint8_t* src, size_t n, int B, float* gray, float* alpha) {
   try {
