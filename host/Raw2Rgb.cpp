@@ -6,6 +6,8 @@
 // 16-bit RGB PNG by --output_bpp), --demosaic_filter (0 bilinear, 2 edge-aware; 1 = DCT is not available), --resize,
 // --disable_tone_curve, --black_level_offset. 8-bit inputs are widened like convert8bitTo16bit (v << 8 | v,
 // CvUtil.cpp:53-66). "Runtime = ... ms" is logged where the reference logs it (Raw2Rgb.cpp:369-373).
+// --device_png (off by default): the output image is encoded on the device behind the ISP (s360_isp_process_png,
+// include/s360_isp_png.h; --output_bpp 8 or 16) and only the file's bytes come back — same pixels in the file.
 // Not produced: the DNG copy (--output_dng_path is accepted and ignored) and readRaw's "raw.tif" side file.
 #include <chrono>
 #include <cstdio>
@@ -40,9 +42,9 @@ int main(int argc, char** argv) {
   std::map<std::string, std::string> F = {{"input_image_path", ""}, {"output_image_path", ""}, {"output_dng_path", ""},
                                           {"isp_config_path", ""}, {"black_level_offset", "0"}, {"demosaic_filter", "2"},
                                           {"resize", "1"}, {"output_bpp", "8"}, {"disable_tone_curve", "false"},
-                                          {"accelerate", "false"}, {"fast", "false"}, {"device", "0"}, {"log_dir", ""},
+                                          {"accelerate", "false"}, {"fast", "false"}, {"device_png", "false"}, {"device", "0"}, {"log_dir", ""},
                                           {"stderrthreshold", "0"}, {"v", "0"}, {"logbuflevel", "0"}};
-  const char* bools[] = {"disable_tone_curve", "accelerate", "fast"};
+  const char* bools[] = {"disable_tone_curve", "accelerate", "fast", "device_png"};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     if (a.size() < 2 || a[0] != '-') die("unexpected argument: " + a);
@@ -119,13 +121,20 @@ int main(int argc, char** argv) {
   s360_isp* isp = nullptr;
   if (s360_isp_create(&isp, std::atoi(F["device"].c_str()), &cfg) < 0) die(s360_last_error(nullptr));
   const int ow = w / cfg.resize, oh = h / cfg.resize;
-  std::vector<uint8_t> out((size_t)ow * oh * 3 * (cfg.output_bpp == 8 ? 1 : 2));
+  const bool devicePng = F["device_png"] == "true" || F["device_png"] == "1";
+  std::vector<uint8_t> out(devicePng ? s360_isp_png_bound(isp, w, h) : (size_t)ow * oh * 3 * (cfg.output_bpp == 8 ? 1 : 2));
+  size_t nfile = 0;
   const auto t0 = std::chrono::steady_clock::now();
-  if (s360_isp_process(isp, raw.data(), w, h, out.data()) < 0) die(s360_last_error(nullptr));
+  if ((devicePng ? s360_isp_process_png(isp, raw.data(), w, h, out.data(), out.size(), &nfile) : s360_isp_process(isp, raw.data(), w, h, out.data())) < 0)
+    die(s360_last_error(nullptr));
   const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   std::fprintf(stderr, "Runtime = %gms\n", ms);
   try {
-    if (cfg.output_bpp == 8) pngio::write(F["output_image_path"], out.data(), ow, oh, 3);
+    if (devicePng) {
+      pngio::OutFile f(F["output_image_path"]);
+      f.put(out.data(), nfile);
+      f.close();
+    } else if (cfg.output_bpp == 8) pngio::write(F["output_image_path"], out.data(), ow, oh, 3);
     else pngio::write16(F["output_image_path"], reinterpret_cast<const uint16_t*>(out.data()), ow, oh);
   } catch (const std::exception& e) {
     die(e.what());

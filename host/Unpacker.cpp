@@ -10,6 +10,9 @@
 // The ISP is the reference Unpacker's: CameraIspPipe(json, fast = false, 16 bits) (Unpacker.cpp:165-183), i.e. the accelerated
 // pipeline's arithmetic (s360_isp_config.pipe = 1: restated from CameraIspGen.cpp, not pinned — include/s360.h). --soft_isp
 // runs the frames through the soft CameraIsp arithmetic instead (pinned bit for bit to CameraIsp.h).
+// --device_png (or S360_UNPACKER_DEVICE_PNG=1 in the environment, for a caller whose command line cannot be changed; off by
+// default): the 16-bit PNG is encoded on the device behind the ISP (s360_isp_process_packed_png, include/s360_isp_png.h) and the
+// camera thread only writes the bytes — same pixels in the files, nothing else changes.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -87,7 +90,7 @@ std::string frame_path(const std::string& dir, uint32_t serial, size_t frame, co
 
 int main(int argc, char** argv) {
   std::map<std::string, std::string> F = {{"isp_dir", ""}, {"output_dir", ""}, {"output_raw_dir", ""}, {"bin_list", ""},
-                                          {"start_frame", "0"}, {"frame_count", "0"}, {"device", "0"}, {"soft_isp", "false"}, {"log_dir", ""},
+                                          {"start_frame", "0"}, {"frame_count", "0"}, {"device", "0"}, {"soft_isp", "false"}, {"device_png", "false"}, {"log_dir", ""},
                                           {"stderrthreshold", "0"}, {"v", "0"}, {"logbuflevel", "0"}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -96,7 +99,7 @@ int main(int argc, char** argv) {
     std::string key = a, val;
     const size_t eq = a.find('=');
     if (eq != std::string::npos) { key = a.substr(0, eq); val = a.substr(eq + 1); }
-    else if (key == "soft_isp") val = "true";  // (a boolean flag)
+    else if (key == "soft_isp" || key == "device_png") val = "true";  // (boolean flags)
     else { if (i + 1 >= argc) die("flag '" + key + "' is missing its argument"); val = argv[++i]; }
     if (!F.count(key)) { std::fprintf(stderr, "ERROR: unknown command line flag '%s'\n", key.c_str()); return 1; }
     F[key] = val;
@@ -106,6 +109,8 @@ int main(int argc, char** argv) {
   const int device = std::atoi(F["device"].c_str());
   const long startFrame = std::atol(F["start_frame"].c_str()), frameCountFlag = std::atol(F["frame_count"].c_str());
   if (startFrame < 0 || frameCountFlag < 0) die("--start_frame and --frame_count must not be negative");
+  const char* envPng = std::getenv("S360_UNPACKER_DEVICE_PNG");
+  const bool devicePng = F["device_png"] == "true" || F["device_png"] == "1" || (envPng && envPng[0] == '1' && !envPng[1]);
 
   std::set<uint32_t> serials;
   std::mutex mu;
@@ -138,7 +143,8 @@ int main(int argc, char** argv) {
           s360_isp* isp = nullptr;
           uint32_t ispSerial = 0;
           std::vector<uint16_t> raw16;
-          std::vector<uint16_t> colored((size_t)w * h * 3);
+          std::vector<uint16_t> colored(devicePng ? 0 : (size_t)w * h * 3);
+          std::vector<uint8_t> file;  // --device_png: the finished PNG file
           for (long f = startFrame; f <= endFrame; ++f) {
             const uint8_t* frame = ff.frame((size_t)f, (size_t)cam);
             uint32_t serial;
@@ -173,6 +179,16 @@ int main(int argc, char** argv) {
               if (s360_isp_config_from_json(ss.str().c_str(), &cfg) < 0) throw std::runtime_error(s360_last_error(nullptr));
               if (s360_isp_create(&isp, device, &cfg) < 0) throw std::runtime_error(s360_last_error(nullptr));
               ispSerial = serial;
+            }
+            if (devicePng) {
+              file.resize(s360_isp_png_bound(isp, w, h));
+              size_t n = 0;
+              if (s360_isp_process_packed_png(isp, frame, bits, w, h, file.data(), file.size(), &n) < 0)
+                throw std::runtime_error(s360_last_error(nullptr));
+              pngio::OutFile out(frame_path(F["output_dir"], serial, (size_t)f, ".png"));
+              out.put(file.data(), n);
+              out.close();
+              continue;
             }
             if (s360_isp_process_packed(isp, frame, bits, w, h, colored.data()) < 0) throw std::runtime_error(s360_last_error(nullptr));
             pngio::write16(frame_path(F["output_dir"], serial, (size_t)f, ".png"), colored.data(), w, h, 1, 1);

@@ -533,4 +533,5 @@ int s360_isp_config_tables(const s360_isp_config* cfg, float* ccm9, float* lut, 
 #include "s360_cubemap.h" /* per-frame cubemap output of the stream / batch hosts */
 #include "s360_state_png.h" /* RGBA and batched PNG encode: the state images of a frame */
 #include "s360_png_decode.h" /* ... and their decode on the device: previous-frame state handed in as files */
+#include "s360_isp_png.h" /* 16-bit PNG encode; the ISP's result as a finished file (the unpack step) */
 #endif /* S360_H_ */

@@ -100,6 +100,10 @@ PNG_DECODE_SYMBOLS = [
     "s360_png_decodable", "s360_decode_png_batch", "s360_png_decode_stats", "s360_png_decode_round_histogram", "s360_png_decode_failure",
     "s360_frame_set_prev_images_png", "s360_frame_set_prev_flow",
 ]
+# ... and every symbol include/s360_isp_png.h declares (16-bit PNG encode, the ISP's result as a finished file; s360.h includes it too)
+ISP_PNG_SYMBOLS = [
+    "s360_png_bound_16", "s360_encode_png16", "s360_isp_png_bound", "s360_isp_process_png", "s360_isp_process_packed_png",
+]
 # ... and the test taps include/s360_debug.h declares (not part of the API)
 DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
 # ... and the one include/s360_debug_final_flow.h declares
@@ -163,6 +167,17 @@ def lib():
                                                      C.POINTER(C.c_size_t)]
         L.s360_frame_set_prev_flow.restype = C.c_int
         L.s360_frame_set_prev_flow.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
+        L.s360_png_bound_16.restype = C.c_size_t
+        L.s360_png_bound_16.argtypes = [C.c_int, C.c_int]
+        L.s360_encode_png16.restype = C.c_int
+        L.s360_encode_png16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.s360_isp_png_bound.restype = C.c_size_t
+        L.s360_isp_png_bound.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.s360_isp_process_png.restype = C.c_int
+        L.s360_isp_process_png.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.s360_isp_process_packed_png.restype = C.c_int
+        L.s360_isp_process_packed_png.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                  C.POINTER(C.c_size_t)]
         L.s360_isp_config_defaults.restype = None
         L.s360_isp_destroy.restype = None
         L.s360_isp_destroy.argtypes = [C.c_void_p]

@@ -1883,6 +1883,77 @@ int s360_isp_process_packed(s360_isp* isp, const uint8_t* frame, int bits, int w
     isp_process_packed(isp, frame, bits, w, h, out_bgr);
   });
 }
+/* ---- 16-bit PNG files, and the ISP's result as a finished PNG file (include/s360_isp_png.h) ---- */
+size_t s360_png_bound_16(int w, int h) {
+  size_t n = 0;
+  (void)guard(nullptr, [&] { n = PngPlan::make(w, h, 3, 16).file_bound; });
+  return n;
+}
+int s360_encode_png16(s360_ctx* c, const uint16_t* bgr16, int w, int h, uint8_t* out, size_t cap, size_t* n_out) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard_l(c, [&](std::unique_lock<std::recursive_mutex>& lk) {
+    need(bgr16 && out && n_out && w > 0 && h > 0, "bad argument");
+    const PngPlan plan = PngPlan::make(w, h, 3, 16);
+    need(cap >= plan.file_bound, "png: output buffer too small (s360_png_bound_16 gives the size to allocate)");
+    const size_t nb = (size_t)w * h * 6;
+    c->op_a.ensure((nb + 3) & ~(size_t)3);
+    c->op_b.ensure(plan.file_bound);
+    S360_HIP(hipMemcpyAsync(c->op_a.p, bgr16, nb, hipMemcpyHostToDevice, c->st));
+    png_encode_enqueue(c->st, c->op_a.as<uint8_t>(), plan, c->op_c, c->op_d, c->op_b.as<uint8_t>());
+    S360_HIP(hipStreamSynchronize(c->st));
+    png_fetch(c, lk, plan, c->op_d, c->op_b, nullptr, nullptr, nullptr, out, cap, n_out, false);  // (the operator scratch stays locked)
+  }, false);
+}
+static PngPlan isp_png_plan(const s360_isp* o, int w, int h) {
+  const int r = o->cfg.resize > 0 ? o->cfg.resize : 1;
+  return PngPlan::make(w / r, h / r, 3, o->cfg.output_bpp == 16 ? 16 : 8);
+}
+size_t s360_isp_png_bound(const s360_isp* isp, int w, int h) {
+  size_t n = 0;
+  if (!isp) return 0;
+  (void)guard(nullptr, [&] { n = isp_png_plan(isp, w, h).file_bound; });
+  return n;
+}
+// The encoder behind the ISP's kernels on the object's stream over `px` (the result on the device), the band table to its page-locked
+// place: first wait. Then the file's bytes: second wait. Then the host's share on the caller's buffer.
+static void isp_png_encode(s360_isp* o, const void* px, const PngPlan& plan, uint8_t* out, size_t cap, size_t* n_out) {
+  const size_t mbytes = ((size_t)plan.nbands + 1) * sizeof(PngBandMeta);
+  if (o->hPngMetaBytes < mbytes) {
+    if (o->hPngMeta) (void)hipHostFree(o->hPngMeta);
+    o->hPngMeta = nullptr;
+    o->hPngMetaBytes = 0;
+    S360_HIP(hipHostMalloc(&o->hPngMeta, mbytes, hipHostMallocDefault));
+    o->hPngMetaBytes = mbytes;
+  }
+  o->dPngFile.ensure(plan.file_bound);
+  png_encode_enqueue(o->st, static_cast<const uint8_t*>(px), plan, o->dPngScratch, o->dPngMeta, o->dPngFile.as<uint8_t>());
+  isp_time_end(o);
+  S360_HIP(hipMemcpyAsync(o->hPngMeta, o->dPngMeta.p, mbytes, hipMemcpyDeviceToHost, o->st));
+  S360_HIP(hipStreamSynchronize(o->st));
+  isp_time_take(o);
+  const PngBandMeta* m = static_cast<const PngBandMeta*>(o->hPngMeta);
+  const size_t end_bands = (size_t)m[plan.nbands].file_off;
+  if (end_bands > plan.file_bound || end_bands + 28 > cap) throw Error(S360_ERR_STATE, "png: the band table names more bytes than the file's bound");
+  S360_HIP(hipMemcpyAsync(out, o->dPngFile.p, end_bands, hipMemcpyDeviceToHost, o->st));
+  S360_HIP(hipStreamSynchronize(o->st));
+  *n_out = png_finish_host(out, cap, plan, m, png_crc_threads());
+}
+int s360_isp_process_png(s360_isp* isp, const uint16_t* raw16, int w, int h, uint8_t* out, size_t cap, size_t* n_out) {
+  return guard(nullptr, [&] {
+    need(isp && raw16 && out && n_out && w > 0 && h > 0, "bad argument");
+    const PngPlan plan = isp_png_plan(isp, w, h);
+    need(cap >= plan.file_bound, "png: output buffer too small (s360_isp_png_bound gives the size to allocate)");
+    isp_png_encode(isp, isp_develop(isp, "s360_isp_process_png", raw16, w, h), plan, out, cap, n_out);
+  });
+}
+int s360_isp_process_packed_png(s360_isp* isp, const uint8_t* frame, int bits, int w, int h, uint8_t* out, size_t cap, size_t* n_out) {
+  return guard(nullptr, [&] {
+    need(isp && frame && out && n_out && w > 0 && h > 0, "bad argument");
+    const PngPlan plan = isp_png_plan(isp, w, h);
+    need(cap >= plan.file_bound, "png: output buffer too small (s360_isp_png_bound gives the size to allocate)");
+    isp_png_encode(isp, isp_develop_packed(isp, "s360_isp_process_packed_png", frame, bits, w, h), plan, out, cap, n_out);
+  });
+}
 int s360_isp_pipe_generated(s360_isp* isp, const s360_camera_isp_gen_args* args) {
   return guard(nullptr, [&] {
     need(isp && args, "null argument");

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -354,7 +355,6 @@ void isp_init(s360_isp* o, int device, const s360_isp_config& cfg) {
   S360_HIP(hipStreamSynchronize(o->st));
 }
 
-static void isp_run_uploaded(s360_isp* o, int inW, int inH, void* out);
 // pixels k_isp_stuck may rewrite per frame (S360_ISP_STUCK_BUDGET; 0 = no bound). Default 262 144: about a second of the serial walk.
 static unsigned stuck_pixel_budget() {
   static const unsigned v = [] {
@@ -367,25 +367,65 @@ static unsigned stuck_pixel_budget() {
 }
 
 static void isp_enqueue(s360_isp* o, hipStream_t st, int inW, int inH);
-void isp_process(s360_isp* o, const uint16_t* raw16, int inW, int inH, void* out) {
-  refuse_while_feeding(o, "s360_isp_process");
+static bool isp_times_on() {
+  static const bool v = [] { const char* e = std::getenv("S360_ISP_TIMES"); return e && e[0] == '1'; }();
+  return v;
+}
+void isp_time_begin(s360_isp* o) {
+  if (!isp_times_on()) return;
+  if (!o->evT0) {
+    S360_HIP(hipEventCreate(&o->evT0));
+    S360_HIP(hipEventCreate(&o->evT1));
+  }
+  S360_HIP(hipEventRecord(o->evT0, o->st));
+}
+void isp_time_end(s360_isp* o) {
+  if (isp_times_on()) S360_HIP(hipEventRecord(o->evT1, o->st));
+}
+void isp_time_take(s360_isp* o) {
+  if (!isp_times_on()) return;
+  float ms = 0;
+  S360_HIP(hipEventElapsedTime(&ms, o->evT0, o->evT1));
+  o->timedMs += ms;
+  o->timedImages += 1;
+}
+const void* isp_develop(s360_isp* o, const char* what, const uint16_t* raw16, int inW, int inH) {
+  refuse_while_feeding(o, what);
   S360_HIP(hipSetDevice(o->device));
   o->dRaw.ensure((size_t)inW * inH * sizeof(uint16_t));
   S360_HIP(hipMemcpyAsync(o->dRaw.p, raw16, (size_t)inW * inH * sizeof(uint16_t), hipMemcpyHostToDevice, o->st));
-  isp_run_uploaded(o, inW, inH, out);
+  isp_time_begin(o);
+  isp_enqueue(o, o->st, inW, inH);
+  return o->dOut.p;
 }
 // Unpacker's per-frame work (Unpacker.cpp:136-143, 169-183): the sensor's packed bytes are widened on the device
-void isp_process_packed(s360_isp* o, const uint8_t* frame, int bits, int inW, int inH, void* out) {
+const void* isp_develop_packed(s360_isp* o, const char* what, const uint8_t* frame, int bits, int inW, int inH) {
   if (bits != 8 && bits != 12) throw Error(S360_ERR_INVALID_ARG, "packed frames are 8 or 12 bits per pixel");
   if (bits == 12 && (inW & 1)) throw Error(S360_ERR_INVALID_ARG, "12-bit packed frames need an even width");
-  refuse_while_feeding(o, "s360_isp_process_packed");
+  refuse_while_feeding(o, what);
   S360_HIP(hipSetDevice(o->device));
   const size_t bytes = bits == 8 ? (size_t)inW * inH : (size_t)inH * (3 * (size_t)inW / 2);
   o->dPacked.ensure(bytes);
   o->dRaw.ensure((size_t)inW * inH * sizeof(uint16_t));
   S360_HIP(hipMemcpyAsync(o->dPacked.p, frame, bytes, hipMemcpyHostToDevice, o->st));
+  isp_time_begin(o);
   isp_launch_unpack(o->st, o->dPacked.as<unsigned char>(), bits, inW, inH, o->dRaw.as<unsigned short>());
-  isp_run_uploaded(o, inW, inH, out);
+  isp_enqueue(o, o->st, inW, inH);
+  return o->dOut.p;
+}
+// ... and the second half: the result to the host, one wait
+static void isp_fetch(s360_isp* o, const void* px, int inW, int inH, void* out) {
+  isp_time_end(o);
+  const size_t outBytes = (size_t)(inW / o->cfg.resize) * (inH / o->cfg.resize) * 3 * (o->cfg.output_bpp == 8 ? 1 : 2);
+  S360_HIP(hipMemcpyAsync(out, px, outBytes, hipMemcpyDeviceToHost, o->st));
+  S360_HIP(hipStreamSynchronize(o->st));
+  isp_time_take(o);
+}
+void isp_process(s360_isp* o, const uint16_t* raw16, int inW, int inH, void* out) {
+  isp_fetch(o, isp_develop(o, "s360_isp_process", raw16, inW, inH), inW, inH, out);
+}
+void isp_process_packed(s360_isp* o, const uint8_t* frame, int bits, int inW, int inH, void* out) {
+  isp_fetch(o, isp_develop_packed(o, "s360_isp_process_packed", frame, bits, inW, inH), inW, inH, out);
 }
 
 // The accelerated pipeline on the frame in dRaw: buffers, launch; the result is left in dOut.
@@ -507,12 +547,6 @@ static void isp_enqueue(s360_isp* o, hipStream_t st, int inW, int inH) {
   }
 }
 
-static void isp_run_uploaded(s360_isp* o, int inW, int inH, void* out) {
-  isp_enqueue(o, o->st, inW, inH);
-  const size_t outBytes = (size_t)(inW / o->cfg.resize) * (inH / o->cfg.resize) * 3 * (o->cfg.output_bpp == 8 ? 1 : 2);
-  S360_HIP(hipMemcpyAsync(out, o->dOut.p, outBytes, hipMemcpyDeviceToHost, o->st));
-  S360_HIP(hipStreamSynchronize(o->st));
-}
 // For callers that keep the result on the device (render.hip: camera images straight into a frame): the raw frame must
 // already be in dRaw (isp_raw_buffer) and everything is enqueued on the caller's stream.
 void* isp_raw_buffer(s360_isp* o, int inW, int inH) {
@@ -544,7 +578,12 @@ const void* isp_enqueue_on(s360_isp* o, hipStream_t st, unsigned long long ctxUi
 }
 
 void isp_release(s360_isp* o) {
+  if (o->timedImages)
+    std::fprintf(stderr, "s360_isp times: %ld images, %.4f ms of device time per image (kernels behind the upload)\n", o->timedImages,
+                 o->timedMs / (double)o->timedImages);
+  if (o->evT0) { (void)hipEventDestroy(o->evT0); (void)hipEventDestroy(o->evT1); o->evT0 = o->evT1 = nullptr; }
   if (o->hStuckCount) { (void)hipHostFree(o->hStuckCount); o->hStuckCount = nullptr; }
+  if (o->hPngMeta) { (void)hipHostFree(o->hPngMeta); o->hPngMeta = nullptr; o->hPngMetaBytes = 0; }
   if (o->st) {
     (void)hipSetDevice(o->device);
     (void)hipStreamSynchronize(o->st);

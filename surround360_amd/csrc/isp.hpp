@@ -74,6 +74,16 @@ struct s360_isp {
   // s360_frame_upload_raw runs this object's kernels on a context's upload stream over the buffers above: the object
   // belongs to the first context it is used with (another context's stream would race on dRaw / dPlane / ...)
   unsigned long long boundCtx = 0;  // uid of the context this object feeds (s360_frame_upload_raw); 0 = none yet
+  // s360_isp_process_png / _packed_png (include/s360_isp_png.h): the PNG encoder's band scratch, band table and file image, and the
+  // band table's page-locked landing place. Allocated on first use, grow only.
+  s360::DevBuf dPngScratch, dPngMeta, dPngFile;
+  void* hPngMeta = nullptr;
+  size_t hPngMetaBytes = 0;
+  // S360_ISP_TIMES=1 (developer switch, tools/unpack_time.py): HIP events around an image's kernels on this object's stream; the sum
+  // is printed to stderr when the object is destroyed
+  hipEvent_t evT0 = nullptr, evT1 = nullptr;
+  double timedMs = 0;
+  long timedImages = 0;
   std::string err;
 };
 
@@ -87,6 +97,15 @@ void isp_init(s360_isp* o, int device, const s360_isp_config& cfg);
 void isp_process(s360_isp* o, const uint16_t* raw16, int w, int h, void* out);
 void isp_process_packed(s360_isp* o, const uint8_t* frame, int bits, int w, int h, void* out);
 void isp_pipe_generated(s360_isp* o, const s360_camera_isp_gen_args& a);
+// The first half of isp_process / isp_process_packed: upload and kernels enqueued on the object's own stream, nothing waits; the
+// result (B,G,R, 8 or 16 bit) is left on the device and returned. `what` names the entry point in a refusal.
+const void* isp_develop(s360_isp* o, const char* what, const uint16_t* raw16, int inW, int inH);
+const void* isp_develop_packed(s360_isp* o, const char* what, const uint8_t* frame, int bits, int inW, int inH);
+// S360_ISP_TIMES=1: isp_time_begin records behind the upload, isp_time_end behind the image's last kernel, isp_time_take (after the
+// stream has been waited for) adds the elapsed time to the object's sum. All three do nothing without the switch.
+void isp_time_begin(s360_isp* o);
+void isp_time_end(s360_isp* o);
+void isp_time_take(s360_isp* o);
 void isp_release(s360_isp* o);
 void* isp_raw_buffer(s360_isp* o, int inW, int inH);
 void* isp_packed_buffer(s360_isp* o, int bits, int inW, int inH);

@@ -1,4 +1,4 @@
-// png.hip — the finished equirect as a PNG file, encoded on the device.
+// png.hip — the finished equirect (and the state images, and the ISP's 16-bit camera images) as PNG files, encoded on the device.
 //
 // What it replaces: imwriteExceptionOnFail(FLAGS_output_equirect_path, ...) at TRSP:938-961 (cv::imwrite's PngEncoder: 8-bit
 // RGB, the Sub filter on every scanline, zlib at Z_BEST_SPEED with Z_RLE — grfmt_png.cpp as the reference's OpenCV sets it).
@@ -44,6 +44,12 @@
 // HBM. Only the two byte reads of a lane (its channel, the same channel one pixel to the left) know C; tokens stay distance-1 byte
 // matches, the tile stays 12288 bytes (4096 or 3072 pixels; with C = 4 a 64-byte group is 16 whole pixels, four lanes share an LDS
 // dword and the reads are conflict-free), Smem and the per-wave bit regions keep their size, the band rule stays one on bytes.
+// C = 6 is 16-bit RGB (IHDR depth 16, colour type 2): interleaved little-endian uint16 B,G,R in — what the ISP leaves on the device with
+// output_bpp 16 — and per pixel six output bytes, sample s = k >> 1 of byte k in R,G,B order, high byte first, i.e. source byte
+// 2 (2 - s) + (1 - (k & 1)) (src_byte); Sub at a distance of 6 bytes, line = 1 + 6 w, a tile is 2048 pixels. A row of an odd-width image
+// starts on a 2-byte boundary only: load_tile takes dwords from the aligned address below, as it does for 3 w. The camera images of
+// the unpack step (host/Unpacker --device_png: png_encode_enqueue behind the ISP's kernels on the ISP object's stream, api.hip). The
+// batch kernel and the decoder (png_decode.hip) stay 8-bit.
 // Batch. C = 0 is the kernel over the bands of MANY images of differing size and channel count (png_batch_enqueue): a device table
 // holds one descriptor per image and the image index of every band, a workgroup looks its band up and runs the C = 3 or C = 4 body.
 // One band launch, one layout launch (a workgroup per image: the prefix sum is segmented), one gather launch; every image gets a
@@ -53,6 +59,7 @@
 //   k_png_band<3>  62 VGPRs  85 SGPRs  occupancy 6 waves/SIMD   (what the kernel had before it became a template)
 //   k_png_band<4>  57 VGPRs  73 SGPRs  occupancy 6
 //   k_png_band<0>  62 VGPRs  92 SGPRs  occupancy 6              (the batch: both bodies behind the table lookup)
+//   k_png_band<6>  62 VGPRs  85 SGPRs  occupancy 6              (16-bit RGB; the three above are what they were before it)
 //   k_png_layout   44 VGPRs  16 SGPRs  4096 B LDS; k_png_gather 8 VGPRs, 27 SGPRs, no LDS
 // Two workgroups of the band kernel fit a CU's 160 KB of LDS: LDS, not registers, bounds the waves in flight.
 #include "png.hpp"
@@ -70,7 +77,7 @@ namespace s360 {
 
 namespace {
 constexpr int kT = 512;                         // threads per workgroup
-constexpr int kTileBytes = 12288;               // bytes of one row per workgroup iteration: 4096 B,G,R or 3072 B,G,R,A pixels
+constexpr int kTileBytes = 12288;               // bytes of one row per workgroup iteration: 4096 B,G,R, 3072 B,G,R,A or 2048 16-bit B,G,R pixels
 constexpr int kRawWords = kTileBytes / 4 + 4;   // a tile's bytes + the pixel to its left + alignment slack
 constexpr int kMaxBits = 15;                    // deflate's longest code
 constexpr int kWaves = kT / 64;
@@ -135,8 +142,17 @@ __device__ inline unsigned rev_bits(unsigned c, int n) {
   return r;
 }
 
+// Where output byte c of a pixel (PNG order) lies in the pixel's C source bytes. C = 3 / 4: R,G,B[,A] out of B,G,R[,A]. C = 6: 16-bit
+// samples, R,G,B out of little-endian B,G,R, every sample high byte first — byte c is sample s = c >> 1, its high byte for even c.
+template <int C>
+__device__ inline int src_byte(int c) {
+  if constexpr (C == 6) return 2 * (2 - (c >> 1)) + (1 - (c & 1));
+  else return c < 3 ? 2 - c : 3;
+}
+
 // Row y's pixels [px0, px0 + kTileBytes / C) and the pixel to their left into S.raw (dwords, coalesced); returns the byte offset
-// of pixel px0 in it. `bgr` is 4-byte aligned, `total` its size.
+// of pixel px0 in it. `bgr` is 4-byte aligned, `total` its size. (A row starts wherever y * w * C falls — on any byte with C = 3, on a
+// 2-byte boundary only with C = 6 and an odd w: the dwords are taken from the aligned address below, `off` is what is left.)
 template <int C>
 __device__ inline int load_tile(Smem& S, const uint8_t* bgr, unsigned long long total, int w, int y, int px0) {
   const unsigned long long rowb = (unsigned long long)y * w * C;
@@ -182,10 +198,10 @@ __device__ inline Tok group_tok(const uint8_t* rawb, int off, int px0, int nbyte
   const int lane = threadIdx.x & 63;
   const bool valid = j < nbytes;
   const int jj = valid ? j : 0;
-  const int p = jj / C, c = jj - C * p;  // pixel of the tile, channel in PNG order (R,G,B[,A] out of B,G,R[,A])
-  const int i = off + C * p + (c < 3 ? 2 - c : 3);
+  const int p = jj / C, c = jj - C * p;  // pixel of the tile, byte of the pixel in PNG order (src_byte: where it lies in the source)
+  const int i = off + C * p + src_byte<C>(c);
   const unsigned cur = rawb[i];
-  const unsigned left = (px0 + p == 0) ? 0u : rawb[i - C];  // Sub: the same channel one pixel to the left, 0 at the row's start
+  const unsigned left = (px0 + p == 0) ? 0u : rawb[i - C];  // Sub: the same byte one pixel to the left, 0 at the row's start
   Tok t;
   t.v = (cur - left) & 255u;
   // the left neighbour's byte: row_bcast:15 brings lanes 15 / 31 / 47 to the first lanes of the next DPP row, row_shr:1 the rest
@@ -290,7 +306,7 @@ __device__ inline unsigned filtered_byte(const uint8_t* bgr, const Geo& G, int y
   const unsigned r = i / G.line, k = i - r * G.line;
   if (k == 0) return 1u;
   const unsigned c = k - 1, p = c / C, ch = c - C * p;
-  const uint8_t* px = bgr + ((unsigned long long)(y0 + r) * G.w + p) * C + (ch < 3 ? 2 - ch : 3);
+  const uint8_t* px = bgr + ((unsigned long long)(y0 + r) * G.w + p) * C + src_byte<C>((int)ch);
   return (unsigned)(px[0] - (p ? px[-C] : 0)) & 255u;
 }
 
@@ -549,7 +565,7 @@ __device__ inline void band_body(Smem& S, const uint8_t* __restrict__ bgr, const
   if (t == 0 && pend) gout[gw] = carry;  // (the last band's final bits; the band's reserve covers the dword)
 }
 
-// C = 3 / 4: one image, a workgroup per band. C = 0: the bands of a batch of images — band_img[blockIdx.x] names the band's image in
+// C = 3 / 4 / 6: one image, a workgroup per band. C = 0: the bands of a batch of images — band_img[blockIdx.x] names the band's image in
 // `imgs`, whose record gives pixels, geometry, channel count and the image's places in the batch's scratch and band tables. Every
 // band is a workgroup of its own and runs for its own rows only: a small image's band leaves its CU as soon as it is done.
 template <int C>
@@ -630,14 +646,16 @@ __global__ __launch_bounds__(kT) void k_png_gather(const uint8_t* __restrict__ s
 inline size_t cdivz(size_t a, size_t b) { return (a + b - 1) / b; }
 }  // namespace
 
-PngPlan PngPlan::make(int w, int h, int channels) {
+PngPlan PngPlan::make(int w, int h, int channels, int depth) {
   if (w < 1 || h < 1 || w > 65535 || h > 65535) throw Error(S360_ERR_INVALID_ARG, "png: unsupported image size");
   if (channels != 3 && channels != 4) throw Error(S360_ERR_INVALID_ARG, "png: channels must be 3 (B,G,R) or 4 (B,G,R,A)");
+  if (depth != 8 && !(depth == 16 && channels == 3)) throw Error(S360_ERR_INVALID_ARG, "png: depth must be 8, or 16 with 3 channels");
   PngPlan p;
   p.w = w;
   p.h = h;
   p.channels = channels;
-  p.line = 1 + (size_t)channels * (size_t)w;
+  p.depth = depth;
+  p.line = 1 + p.pixel_bytes() * (size_t)w;
   // ~192 KB of scanlines per band, at least ~64 bands in a tall image (small frames still spread over the chip)
   const size_t by_size = std::max<size_t>(1, ((size_t)192 << 10) / p.line), by_count = cdivz((size_t)h, 64);
   p.rows_per_band = (int)std::max<size_t>(1, std::min(std::min(by_size, by_count), (size_t)h));
@@ -656,7 +674,7 @@ Geo geo_of(const PngPlan& P) {
   G.w = P.w; G.h = P.h; G.rows_per_band = P.rows_per_band; G.nbands = P.nbands;
   G.line = (unsigned)P.line;
   G.band_stride = P.band_stride;
-  G.total_bytes = (unsigned long long)P.w * P.h * P.channels;
+  G.total_bytes = (unsigned long long)P.w * P.h * P.pixel_bytes();
   return G;
 }
 }  // namespace
@@ -668,7 +686,9 @@ void png_encode_enqueue(hipStream_t st, const uint8_t* bgr, const PngPlan& P, De
   const Geo G = geo_of(P);
   const BatchImage* none = nullptr;
   const int* nomap = nullptr;
-  if (P.channels == 4)
+  if (P.depth == 16)
+    hipLaunchKernelGGL(k_png_band<6>, dim3(P.nbands), dim3(kT), 0, st, bgr, G, scratch.as<uint8_t>(), meta.as<PngBandMeta>(), none, nomap);
+  else if (P.channels == 4)
     hipLaunchKernelGGL(k_png_band<4>, dim3(P.nbands), dim3(kT), 0, st, bgr, G, scratch.as<uint8_t>(), meta.as<PngBandMeta>(), none, nomap);
   else
     hipLaunchKernelGGL(k_png_band<3>, dim3(P.nbands), dim3(kT), 0, st, bgr, G, scratch.as<uint8_t>(), meta.as<PngBandMeta>(), none, nomap);
@@ -682,6 +702,7 @@ PngBatchPlan PngBatchPlan::make(const std::vector<PngPlan>& plans) {
   PngBatchPlan B;
   B.img = plans;
   for (const PngPlan& P : plans) {
+    if (P.depth != 8) throw Error(S360_ERR_INVALID_ARG, "png: the batch encoder takes 8-bit images only");
     B.band0.push_back(B.nbands);
     B.scratch_off.push_back(B.scratch_bytes);
     B.meta0.push_back(B.meta_records);
@@ -783,7 +804,7 @@ size_t png_finish_host(uint8_t* file, size_t cap, const PngPlan& P, const PngBan
   uint8_t ihdr[13];
   be32(ihdr, (uint32_t)P.w);
   be32(ihdr + 4, (uint32_t)P.h);
-  ihdr[8] = 8; ihdr[9] = P.channels == 4 ? 6 : 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;  // 8-bit RGB / RGBA, deflate, adaptive filtering, not interlaced
+  ihdr[8] = (uint8_t)P.depth; ihdr[9] = P.channels == 4 ? 6 : 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;  // 8- / 16-bit RGB or 8-bit RGBA, deflate, adaptive filtering, not interlaced
   at += put_chunk(file + at, "IHDR", ihdr, 13);
   uint8_t br[4];
   be32(br, (uint32_t)P.rows_per_band);

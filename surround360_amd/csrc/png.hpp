@@ -11,14 +11,17 @@
 namespace s360 {
 
 // Geometry of one encode: an 8-bit B,G,R (channels = 3) or B,G,R,A (channels = 4) image of w x h pixels (rows contiguous) becomes
-// an 8-bit RGB (colour type 2) or RGBA (colour type 6, alpha kept) PNG whose scanlines are deflated in bands of `rows_per_band`
+// an 8-bit RGB (colour type 2) or RGBA (colour type 6, alpha kept) PNG — or a 16-bit B,G,R image (depth = 16: the ISP's output_bpp 16
+// result, 6 bytes per pixel) a 16-bit RGB PNG, Sub at a distance of 6 bytes — whose scanlines are deflated in bands of `rows_per_band`
 // rows, one workgroup and one IDAT chunk per band. The band rule is one on bytes: ~192 KB of scanlines, at least ~64 bands.
 struct PngPlan {
   int w = 0, h = 0, rows_per_band = 0, nbands = 0, channels = 3;
-  size_t line = 0;         // bytes of a filtered scanline: 1 + channels x w
+  int depth = 8;           // bits per sample: 8, or 16 with channels = 3 (little-endian uint16 B,G,R in, big-endian R,G,B samples out)
+  size_t pixel_bytes() const { return (size_t)channels * (size_t)(depth / 8); }
+  size_t line = 0;         // bytes of a filtered scanline: 1 + pixel_bytes x w
   size_t band_stride = 0;  // bytes reserved per band in the scratch (a band coded as stored blocks always fits)
   size_t file_bound = 0;   // upper bound of the file's size
-  static PngPlan make(int w, int h, int channels = 3);
+  static PngPlan make(int w, int h, int channels = 3, int depth = 8);
 };
 // n images of differing size and channel count encoded by ONE launch sequence (png_batch_enqueue): where every image's bands,
 // band table (nbands + 1 records) and file image (file_bound bytes, 16-byte aligned) lie in the batch's buffers.

@@ -67,6 +67,33 @@ class CameraIsp:
                                             out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def png_bound(self, w, h):
+        """s360_isp_png_bound: the size to allocate for the file of a w x h input through this object."""
+        return int(lib().s360_isp_png_bound(self.h, int(w), int(h)))
+
+    def get_png(self, raw16, out=None):
+        """s360_isp_process_png: get_image's result as the bytes of a finished PNG file (16-bit RGB with output_bpp 16, 8-bit RGB with
+        8), encoded on the device behind the ISP; the pixels never reach the host. `out`: a uint8 buffer to encode into (default: one
+        of png_bound's size; a smaller one is refused); returns a view of the file's bytes in it."""
+        raw = np.ascontiguousarray(raw16, np.uint16)
+        hh, ww = raw.shape
+        if out is None:
+            out = np.empty(max(self.png_bound(ww, hh), 1), np.uint8)
+        n = C.c_size_t(0)
+        check(lib().s360_isp_process_png(self.h, raw.ctypes.data_as(C.c_void_p), ww, hh, out.ctypes.data_as(C.c_void_p),
+                                         C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value]
+
+    def get_png_packed(self, frame, bits, w, h, out=None):
+        """s360_isp_process_packed_png: the same from the sensor's packed bytes (get_image_packed's input)."""
+        fr = np.ascontiguousarray(frame, np.uint8)
+        if out is None:
+            out = np.empty(max(self.png_bound(w, h), 1), np.uint8)
+        n = C.c_size_t(0)
+        check(lib().s360_isp_process_packed_png(self.h, fr.ctypes.data_as(C.c_void_p), bits, w, h, out.ctypes.data_as(C.c_void_p),
+                                                C.c_size_t(out.size), C.byref(n)))
+        return out[:n.value]
+
     def close(self):
         if self.h:
             lib().s360_isp_destroy(self.h)

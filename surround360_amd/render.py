@@ -464,6 +464,19 @@ class Context:
         self._ck(lib().s360_encode_png_c(self.h, _p(px), w, h, ch, _p(out), C.c_size_t(cap), C.byref(n)))
         return out[:n.value].tobytes()
 
+    def encode_png16(self, bgr16, cap=None):
+        """s360_encode_png16: an (h, w, 3) uint16 B,G,R image -> the bytes of a 16-bit RGB PNG file, encoded on the device. `cap`: the
+        buffer size to offer instead of s360_png_bound_16 (a smaller one is refused)."""
+        px = np.ascontiguousarray(bgr16, np.uint16)
+        h, w = px.shape[:2]
+        assert px.shape == (h, w, 3)
+        bound = int(lib().s360_png_bound_16(w, h))
+        cap = bound if cap is None else int(cap)
+        out = np.empty(max(bound, cap, 1), np.uint8)
+        n = C.c_size_t(0)
+        self._ck(lib().s360_encode_png16(self.h, _p(px), w, h, _p(out), C.c_size_t(cap), C.byref(n)))
+        return out[:n.value].tobytes()
+
     def encode_png_batch(self, images):
         """s360_encode_png_batch: a list of (h, w, 3) / (h, w, 4) uint8 images of any sizes -> the list of their PNG files, encoded
         by one launch sequence on the device."""
