@@ -42,6 +42,31 @@ enum CoverageCounter {
   COV_MEDIAN_SIGNED_ZEROS,// medianBlur5 windows that hold both +0 and -0
   COV_SEARCH_TIE,         // adjustInitialFlow: a candidate whose patch error equals the best so far
   COV_SEARCH_NONFINITE,   // adjustInitialFlow: a non-finite intensity ratio or patch error
+  // the soft ISP (isp.h: ispRun) ...
+  COV_ISP_FLAG_TIE,       // demosaicEdgeAware: dH == dV (the flag's `<=` decides)
+  COV_ISP_VOTE_39,        // the 9 x 9 vote counts 39 (the last count that takes gV) ...
+  COV_ISP_VOTE_40,        // ... or 40 (the first that takes gH)
+  COV_ISP_CLAMP_LO,       // whiteBalance / clampAndStretch: a sample below 0 or clampMin
+  COV_ISP_CLAMP_HI,       // ... above 1 or clampMax
+  COV_ISP_RAW_GE_ONE,     // blackLevelAdjust: a raw sample of 1.0 (full scale), which the adjustment skips
+  COV_ISP_LUT_FIRST,      // colorCorrect: tone table entry 0 ...
+  COV_ISP_LUT_LAST,       // ... or 4095
+  COV_ISP_CORE_ZERO,      // sharpenWithIirLowPass: hp == 0
+  COV_ISP_CORE_SATURATED, // ... a noise gain of exactly 1
+  COV_ISP_OUT_AT_MAX,     // getImage: a sample at the output type's maximum
+  COV_ISP_IIR_CLAMPED,    // the low pass's clamp to [0, maxVal] changed a value
+  // ... and the accelerated pipeline's equivalents (isp_pipe.h: ispPipeRun; its low pass clamps nothing, its raw samples all
+  // go through A (x - B))
+  COV_PIPE_FLAG_TIE,
+  COV_PIPE_VOTE_39,
+  COV_PIPE_VOTE_40,
+  COV_PIPE_CLAMP_LO,
+  COV_PIPE_CLAMP_HI,
+  COV_PIPE_LUT_FIRST,
+  COV_PIPE_LUT_LAST,
+  COV_PIPE_CORE_ZERO,
+  COV_PIPE_CORE_SATURATED,
+  COV_PIPE_OUT_AT_MAX,
   COV_COUNT
 };
 static inline std::atomic<unsigned long long>* coverageCounters() {

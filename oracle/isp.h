@@ -21,6 +21,8 @@
 #include <stdexcept>
 #include <vector>
 
+#include "cvlite.h"  // the coverage counters
+
 namespace orc {
 
 constexpr int kIspToneLutSize = 4096;  // kToneCurveLutSize, CameraIsp.h:42
@@ -165,9 +167,21 @@ inline void ispUnpackFrame(int bits, const uint8_t* frame, int w, int h, uint16_
   }
 }
 
+// Where ispRun leaves its intermediates for a caller that asks (tests: the library's kernels are held to them bit for bit,
+// tests/test_gpu_isp_stages.py). Every pointer may be null; the planes are those of the computation that produces `out`, copied
+// at the moment they are final. All are height x width of the OUTPUT (after resize); tone / lowRow / low hold 3 floats per pixel
+// (r, g, b). flag, gV, gH and green exist with the edge-aware demosaic only, lowRow and low only where sharpening runs.
+struct IspStages {
+  float* plane = nullptr;   // the normalised Bayer plane after clampAndStretch (after removeStuckPixels where it runs)
+  uint8_t* flag = nullptr;  // dH <= dV
+  float *gV = nullptr, *gH = nullptr, *green = nullptr;
+  float* tone = nullptr;    // the tone-mapped image before sharpening
+  float *lowRow = nullptr, *low = nullptr;  // the low pass after the row direction / after both directions
+};
+
 // One frame through CameraIsp::loadImage + getImage(swizzle = true). raw: inH x inW uint16. out: (inH/resize) x
 // (inW/resize) x 3 in B,G,R order, uint8 (outputBpp 8) or uint16 bit patterns (outputBpp 16).
-inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, void* out) {
+inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, void* out, const IspStages* stages = nullptr) {
   using namespace isp_detail;
   if (c.demosaicFilter != 0 && c.demosaicFilter != 2) throw std::runtime_error("isp oracle: demosaic filter 1 (DCT) is not restated");
   if (c.resize != 1 && c.resize != 2 && c.resize != 4 && c.resize != 8) throw std::runtime_error("expecting a resize value of 1, 2, 4, or 8");
@@ -176,6 +190,9 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
   const int maxDimension = std::max(width, height);
   const int maxPixelValue = 65535;  // loadImage, 16-bit input (CameraIsp.h:845-849)
   const size_t n = (size_t)width * height;
+  const IspStages noStages;
+  const IspStages& S = stages ? *stages : noStages;
+  auto hand = [&](float* dst, const std::vector<float>& src) { if (dst) std::copy(src.begin(), src.end(), dst); };
   auto redPixel = [&](int i, int j) { return T.red[i % 2][j % 2]; };
   auto greenPixel = [&](int i, int j) { return T.green[i % 2][j % 2]; };
   std::vector<float> rawImage(n);
@@ -210,6 +227,8 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
           if (redPixel(i, j)) RAW(i, j) = (RAW(i, j) - br) * sr;
           else if (greenPixel(i, j)) RAW(i, j) = (RAW(i, j) - bg) * sg;
           else RAW(i, j) = (RAW(i, j) - bb) * sb;
+        } else {
+          coverageHit(COV_ISP_RAW_GE_ONE);
         }
   }
   {  // antiVignette (CameraIsp.h:1145-1154)
@@ -228,8 +247,10 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
     for (int j = 0; j < width; ++j) {
       const int ch = redPixel(i, j) ? 0 : greenPixel(i, j) ? 1 : 2;
       float v = RAW(i, j) * c.whiteBalanceGain[ch];
-      v = clampf(v, 0.0f, 1.0f);
       const float lo = c.clampMin[ch], hi = c.clampMax[ch];
+      if (v < 0.0f || v < lo) coverageHit(COV_ISP_CLAMP_LO);
+      if (v > 1.0f || v > hi) coverageHit(COV_ISP_CLAMP_HI);
+      v = clampf(v, 0.0f, 1.0f);
       v = clampf(v, lo, hi);
       RAW(i, j) = (v - lo) / (hi - lo);
     }
@@ -276,6 +297,7 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
       }
     }
   }
+  hand(S.plane, rawImage);
   // demosaic (CameraIsp.h:1156-1212): planes r, g, b hold the raw value at their own Bayer sites
   std::vector<float> r(n, 0.0f), g(n, 0.0f), b(n, 0.0f);
   auto AT = [&](std::vector<float>& m, int i, int j) -> float& { return m[(size_t)i * width + j]; };
@@ -332,6 +354,14 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
         }
       }
     }
+    std::vector<uint8_t> homog(n);  // dH <= dV, once per pixel (the vote below reads each 81 times)
+    for (size_t p = 0; p < n; ++p) {
+      homog[p] = dH[p] <= dV[p];
+      if (dH[p] == dV[p]) coverageHit(COV_ISP_FLAG_TIE);
+    }
+    if (S.flag) std::copy(homog.begin(), homog.end(), S.flag);
+    hand(S.gV, gV);
+    hand(S.gH, gH);
     const int w = 4, diameter = 2 * w + 1, diameterSquared = diameter * diameter;
     for (int i = 0; i < height; ++i)
       for (int j = 0; j < width; ++j) {
@@ -340,11 +370,14 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
           const int il = reflecti(i + l, height);
           for (int k = -w; k <= w; ++k) {
             const int jk = reflecti(j + k, width);
-            hCount += (AT(dH, il, jk) <= AT(dV, il, jk));
+            hCount += homog[(size_t)il * width + jk];
           }
         }
+        if (hCount == diameterSquared / 2 - 1) coverageHit(COV_ISP_VOTE_39);
+        if (hCount == diameterSquared / 2) coverageHit(COV_ISP_VOTE_40);
         AT(g, i, j) = hCount < diameterSquared / 2 ? AT(gV, i, j) : AT(gH, i, j);
       }
+    hand(S.green, g);
     std::vector<float> rmg(n, 0.0f), bmg(n, 0.0f);  // red - green, blue - green at their own sites
     for (int i = 0; i < height; ++i)
       for (int j = 0; j < width; ++j) {
@@ -384,9 +417,12 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
     for (int k = 0; k < 3; ++k) {
       const float v = T.compositeCCM[k * 3] * pr + T.compositeCCM[k * 3 + 1] * pgv + T.compositeCCM[k * 3 + 2] * pb;
       const int idx = (int)clampf(v, 0.0f, lutRange);  // vector index: float -> size_t by truncation
+      if (idx == 0) coverageHit(COV_ISP_LUT_FIRST);
+      if (idx == kIspToneLutSize - 1) coverageHit(COV_ISP_LUT_LAST);
       img[p * 3 + k] = T.toneLut[(size_t)idx * 3 + k];
     }
   }
+  hand(S.tone, img);
   // sharpen (CameraIsp.h:1244-1259; Filter.h:38-126): two-tap IIR low pass with reflected boundaries, unsharp mask
   if (c.sharpening[0] != 0.0 && c.sharpening[1] != 0.0 && c.sharpening[2] != 0.0) {
     const float maxVal = (1 << c.outputBpp) - 1.0f;
@@ -402,9 +438,14 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
       for (int j = width - 2; j >= -1; --j) {
         const float* ip = &buffer[(size_t)reflecti(j, width) * 3];
         float* o = &lp[((size_t)i * width + j + 1) * 3];
-        for (int k = 0; k < 3; ++k) { v[k] = ip[k] * (1.0f - alpha) + v[k] * alpha; o[k] = clampf(v[k], 0.0f, maxVal); }
+        for (int k = 0; k < 3; ++k) {
+          v[k] = ip[k] * (1.0f - alpha) + v[k] * alpha;
+          if (v[k] < 0.0f || v[k] > maxVal) coverageHit(COV_ISP_IIR_CLAMPED);
+          o[k] = clampf(v[k], 0.0f, maxVal);
+        }
       }
     }
+    hand(S.lowRow, lp);
     for (int j = 0; j < width; ++j) {  // vertical, in place on lp
       float v[3] = {lp[(size_t)j * 3], lp[(size_t)j * 3 + 1], lp[(size_t)j * 3 + 2]};
       for (int i = 1; i <= height; ++i) {
@@ -415,14 +456,21 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
       for (int i = height - 2; i >= -1; --i) {
         const float* ip = &buffer[(size_t)reflecti(i, height) * 3];
         float* o = &lp[((size_t)(i + 1) * width + j) * 3];
-        for (int k = 0; k < 3; ++k) { v[k] = ip[k] * (1.0f - alpha) + v[k] * alpha; o[k] = clampf(v[k], 0.0f, maxVal); }
+        for (int k = 0; k < 3; ++k) {
+          v[k] = ip[k] * (1.0f - alpha) + v[k] * alpha;
+          if (v[k] < 0.0f || v[k] > maxVal) coverageHit(COV_ISP_IIR_CLAMPED);
+          o[k] = clampf(v[k], 0.0f, maxVal);
+        }
       }
     }
+    hand(S.low, lp);
     const float amount[3] = {1.0f + c.sharpening[0], 1.0f + c.sharpening[1], 1.0f + c.sharpening[2]};
     for (size_t p = 0; p < n * 3; ++p) {  // sharpenWithIirLowPass (Filter.h:92-126)
       const int k = (int)(p % 3);
       const float hp = img[p] - lp[p];
       const float ng = 1.0f - expf(-((hp * hp) * c.noiseCore));
+      if (hp == 0.0f) coverageHit(COV_ISP_CORE_ZERO);
+      if (ng == 1.0f) coverageHit(COV_ISP_CORE_SATURATED);
       img[p] = clampf(lp[p] + hp * ng * amount[k], 0.0f, maxVal);
     }
   }
@@ -430,6 +478,7 @@ inline void ispRun(const IspConfig& c, const uint16_t* raw, int inW, int inH, vo
   for (size_t p = 0; p < n; ++p)
     for (int k = 0; k < 3; ++k) {
       const float v = img[p * 3 + k];
+      if (v >= float((1 << c.outputBpp) - 1)) coverageHit(COV_ISP_OUT_AT_MAX);
       if (c.outputBpp == 8) reinterpret_cast<uint8_t*>(out)[p * 3 + (2 - k)] = (uint8_t)(int)v;
       else reinterpret_cast<uint16_t*>(out)[p * 3 + (2 - k)] = (uint16_t)(int)v;
     }

@@ -426,6 +426,31 @@ int orc_isp_pipe_run(const IspConfig* cfg, int fast, const uint16_t* raw, int w,
     return -1;
   }
 }
+// ... and the same two runs handing out their intermediates (isp.h: IspStages, isp_pipe.h: IspPipeStages; any pointer may be null)
+int orc_isp_run_stages(const IspConfig* cfg, const uint16_t* raw, int w, int h, void* out, float* plane, uint8_t* flag, float* gV,
+                       float* gH, float* green, float* tone, float* lowRow, float* low, char* err, int err_cap) {
+  try {
+    IspStages s;
+    s.plane = plane; s.flag = flag; s.gV = gV; s.gH = gH; s.green = green; s.tone = tone; s.lowRow = lowRow; s.low = low;
+    ispRun(*cfg, raw, w, h, out, &s);
+    return 0;
+  } catch (const std::exception& e) {
+    if (err && err_cap > 0) { std::strncpy(err, e.what(), err_cap - 1); err[err_cap - 1] = 0; }
+    return -1;
+  }
+}
+int orc_isp_pipe_run_stages(const IspConfig* cfg, int fast, const uint16_t* raw, int w, int h, void* out, float* site, uint8_t* flag,
+                            float* green, float* tone, float* lowY, float* low, char* err, int err_cap) {
+  try {
+    IspPipeStages s;
+    s.site = site; s.flag = flag; s.green = green; s.tone = tone; s.lowY = lowY; s.low = low;
+    ispPipeRun(*cfg, fast != 0, raw, w, h, out, true, &s);
+    return 0;
+  } catch (const std::exception& e) {
+    if (err && err_cap > 0) { std::strncpy(err, e.what(), err_cap - 1); err[err_cap - 1] = 0; }
+    return -1;
+  }
+}
 void orc_isp_unpack_frame(int bits, const uint8_t* frame, int w, int h, uint16_t* out) { ispUnpackFrame(bits, frame, w, h, out); }
 void orc_isp_tables(const IspConfig* cfg, float* ccm9, float* lut /*4096 x 3*/) {
   const IspTables t = ispSetup(*cfg);

@@ -108,6 +108,8 @@ ISP_PNG_SYMBOLS = [
 DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
 # ... and the one include/s360_debug_final_flow.h declares
 DEBUG_FINAL_FLOW_SYMBOLS = ["s360_debug_upscale_blur"]
+# ... and the one include/s360_debug_isp.h declares
+DEBUG_ISP_SYMBOLS = ["s360_debug_isp_stages"]
 
 _lib = None
 
@@ -178,6 +180,8 @@ def lib():
         L.s360_isp_process_packed_png.restype = C.c_int
         L.s360_isp_process_packed_png.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                                   C.POINTER(C.c_size_t)]
+        L.s360_debug_isp_stages.restype = C.c_int
+        L.s360_debug_isp_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8
         L.s360_isp_config_defaults.restype = None
         L.s360_isp_destroy.restype = None
         L.s360_isp_destroy.argtypes = [C.c_void_p]

@@ -11,6 +11,7 @@
 #include "../../include/s360.h"
 #include "../../include/s360_debug.h"
 #include "../../include/s360_debug_final_flow.h"
+#include "../../include/s360_debug_isp.h"
 #include "ctx.hpp"
 #include "isp.hpp"
 #include "render.hpp"
@@ -1881,6 +1882,16 @@ int s360_isp_process_packed(s360_isp* isp, const uint8_t* frame, int bits, int w
   return guard(nullptr, [&] {
     need(isp && frame && out_bgr && w > 0 && h > 0, "bad argument");
     isp_process_packed(isp, frame, bits, w, h, out_bgr);
+  });
+}
+// test tap (include/s360_debug_isp.h): the ISP's intermediates where the product's own launch sequence leaves them
+int s360_debug_isp_stages(s360_isp* isp, const uint16_t* raw16, int w, int h, int stop_after, float* plane, uint8_t* flag, float* gv,
+                          float* gh, float* green, float* tone, float* low, void* out_bgr) {
+  return guard(nullptr, [&] {
+    need(isp && raw16 && w > 0 && h > 0, "bad argument");
+    IspStageOut s;
+    s.plane = plane; s.gv = gv; s.gh = gh; s.green = green; s.tone = tone; s.low = low; s.flag = flag; s.out = out_bgr;
+    isp_debug_stages(isp, raw16, w, h, stop_after, s);
   });
 }
 /* ---- 16-bit PNG files, and the ISP's result as a finished PNG file (include/s360_isp_png.h) ---- */

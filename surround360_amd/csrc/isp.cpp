@@ -233,7 +233,7 @@ void isp_derive(const s360_isp_config& cfg, IspDev& d, std::vector<float>& lut) 
 }
 
 static void pipe_enqueue(s360_isp* o, hipStream_t st, const IspPipeDev& d, int w, int h, const float* vigH, const float* vigV,
-                         const unsigned short* toneTab);
+                         const unsigned short* toneTab, int stopAfter = 0);
 // The scalar preamble of the generated pipeline (CameraIspGen.cpp:318-337, 569-571, 605) from the parameters it is called with
 static void pipe_preamble(IspPipeDev& p, const float* black, const float* wb, const float* cmin, const float* cmax,
                           const float* sharpening, float support, float noiseCore, const float* ccm9) {
@@ -366,7 +366,7 @@ static unsigned stuck_pixel_budget() {
   return v;
 }
 
-static void isp_enqueue(s360_isp* o, hipStream_t st, int inW, int inH);
+static void isp_enqueue(s360_isp* o, hipStream_t st, int inW, int inH, int stopAfter = 0);
 static bool isp_times_on() {
   static const bool v = [] { const char* e = std::getenv("S360_ISP_TIMES"); return e && e[0] == '1'; }();
   return v;
@@ -430,7 +430,7 @@ void isp_process_packed(s360_isp* o, const uint8_t* frame, int bits, int inW, in
 
 // The accelerated pipeline on the frame in dRaw: buffers, launch; the result is left in dOut.
 static void pipe_enqueue(s360_isp* o, hipStream_t st, const IspPipeDev& d, int w, int h, const float* vigH, const float* vigV,
-                         const unsigned short* toneTab) {
+                         const unsigned short* toneTab, int stopAfter) {
   const size_t n = (size_t)w * h;
   o->dOut.ensure(n * 3 * (d.outputBpp == 8 ? 1 : 2));
   o->dPlane.ensure((size_t)(w + 16) * (h + 16) * sizeof(float));
@@ -454,12 +454,12 @@ static void pipe_enqueue(s360_isp* o, hipStream_t st, const IspPipeDev& d, int w
   P.vigV = vigV;
   P.toneTab = toneTab;
   P.exptab = o->dExp.as<unsigned long long>();
-  isp_pipe_launch(st, d, o->dRaw.as<unsigned short>(), w, h, P, o->dOut.p);
+  isp_pipe_launch(st, d, o->dRaw.as<unsigned short>(), w, h, P, o->dOut.p, stopAfter);
   S360_HIP(hipGetLastError());
 }
 
 // Enqueues the ISP of the frame already in dRaw on `st`; the result (B,G,R, 8 or 16 bit) is left in dOut.
-static void isp_enqueue(s360_isp* o, hipStream_t st, int inW, int inH) {
+static void isp_enqueue(s360_isp* o, hipStream_t st, int inW, int inH, int stopAfter) {
   const s360_isp_config& cfg = o->cfg;
   const int w = inW / cfg.resize, h = inH / cfg.resize;
   // the 9x9 homogeneity window and the reflected +-2 taps index up to 4 pixels past an edge (the reference reads out
@@ -488,7 +488,7 @@ static void isp_enqueue(s360_isp* o, hipStream_t st, int inW, int inH) {
   }
   const size_t outBytes = n * 3 * (cfg.output_bpp == 8 ? 1 : 2);
   if (cfg.pipe) {
-    pipe_enqueue(o, st, o->pipe, w, h, cur->h_.as<float>(), cur->v_.as<float>(), o->dToneTab.as<unsigned short>());
+    pipe_enqueue(o, st, o->pipe, w, h, cur->h_.as<float>(), cur->v_.as<float>(), o->dToneTab.as<unsigned short>(), stopAfter);
     return;
   }
   o->dPlane.ensure(n * sizeof(float));
@@ -531,7 +531,7 @@ static void isp_enqueue(s360_isp* o, hipStream_t st, int inW, int inH) {
   B.exptab = o->dExp.as<unsigned long long>();
   B.stuckCount = o->dStuckCount.as<unsigned>();
   B.stuckBudget = stuck_pixel_budget();
-  isp_launch(st, o->dev, o->dRaw.as<unsigned short>(), inW, inH, B, o->dOut.p);
+  isp_launch(st, o->dev, o->dRaw.as<unsigned short>(), inW, inH, B, o->dOut.p, stopAfter);
   S360_HIP(hipGetLastError());
   if (o->dev.stuckR > 0 && B.stuckBudget) {
     // removeStuckPixels where it changes pixels is a serial walk (k_isp_stuck): the one configuration of the ISP whose cost is not
@@ -545,6 +545,39 @@ static void isp_enqueue(s360_isp* o, hipStream_t st, int inW, int inH) {
                                             std::to_string(B.stuckBudget) + ", ~1-5 us each in one workgroup): refused; S360_ISP_STUCK_BUDGET=<pixels> "
                                             "raises the budget, 0 removes it");
   }
+}
+
+// The test tap (include/s360_debug_isp.h): isp_process's upload and launch sequence — through isp_enqueue, so sizes, buffers and
+// the stuck-pixel verdict are the product's —, then the buffers the sequence leaves behind, copied where the caller asked.
+void isp_debug_stages(s360_isp* o, const uint16_t* raw16, int inW, int inH, int stopAfter, const IspStageOut& S) {
+  const s360_isp_config& cfg = o->cfg;
+  if (stopAfter != 0 && stopAfter != 1) throw Error(S360_ERR_INVALID_ARG, "stop_after is 0 (the whole sequence) or 1 (after the low pass's first direction)");
+  const bool pipe = cfg.pipe != 0, fast = cfg.pipe == 2;
+  const bool hasVote = pipe ? !fast : cfg.demosaic_filter == 2;  // flag, green (and the soft ISP's gV / gH)
+  const bool hasLow = pipe ? !fast : o->dev.sharpen != 0;
+  if ((S.gv || S.gh) && (pipe || !hasVote)) throw Error(S360_ERR_INVALID_ARG, "gv / gh exist in the soft ISP with demosaic_filter 2 only");
+  if ((S.flag || S.green) && !hasVote) throw Error(S360_ERR_INVALID_ARG, "flag / green: this configuration runs no homogeneity vote");
+  if ((S.low || stopAfter == 1) && !hasLow) throw Error(S360_ERR_INVALID_ARG, "low / stop_after 1: this configuration runs no low pass");
+  if (stopAfter == 1 && S.out) throw Error(S360_ERR_INVALID_ARG, "stop_after 1 produces no output image");
+  refuse_while_feeding(o, "s360_debug_isp_stages");
+  S360_HIP(hipSetDevice(o->device));
+  o->dRaw.ensure((size_t)inW * inH * sizeof(uint16_t));
+  S360_HIP(hipMemcpyAsync(o->dRaw.p, raw16, (size_t)inW * inH * sizeof(uint16_t), hipMemcpyHostToDevice, o->st));
+  isp_enqueue(o, o->st, inW, inH, stopAfter);
+  const int w = inW / cfg.resize, h = inH / cfg.resize;
+  const size_t n = (size_t)w * h;
+  auto fetch = [&](void* dst, const DevBuf& src, size_t bytes) {
+    if (dst) S360_HIP(hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, o->st));
+  };
+  fetch(S.plane, o->dPlane, (pipe ? (size_t)(w + 16) * (h + 16) : n) * sizeof(float));
+  fetch(S.flag, o->dFlag, pipe ? (size_t)(w + 12) * (h + 12) : n);
+  fetch(S.gv, o->dGV, n * sizeof(float));
+  fetch(S.gh, o->dGH, n * sizeof(float));
+  fetch(S.green, o->dGreen, (pipe ? (size_t)(w + 4) * (h + 4) : n) * sizeof(float));
+  fetch(S.tone, o->dImg, n * 3 * sizeof(float));
+  fetch(S.low, o->dLp, n * 3 * sizeof(float));
+  fetch(S.out, o->dOut, n * 3 * (cfg.output_bpp == 8 ? 1 : 2));
+  S360_HIP(hipStreamSynchronize(o->st));
 }
 
 // For callers that keep the result on the device (render.hip: camera images straight into a frame): the raw frame must

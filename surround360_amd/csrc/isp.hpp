@@ -44,11 +44,13 @@ struct IspPipeBufs {
   const unsigned short* toneTab;                        // [4096][3]: the tone curve truncated to the output type
   const unsigned long long* exptab;
 };
+// stopAfter (the test tap s360_debug_isp_stages only; 0 everywhere else): 1 = return after the low pass's first direction, whose
+// result the second direction overwrites. Nothing is launched differently up to there.
 void isp_pipe_launch(hipStream_t st, const IspPipeDev& d, const unsigned short* raw, int w, int h, const IspPipeBufs& B,
-                     void* out);
+                     void* out, int stopAfter = 0);
 void isp_launch_unpack(hipStream_t st, const unsigned char* frame, int bits, int w, int h, unsigned short* out);
 void isp_launch(hipStream_t st, const IspDev& d, const unsigned short* raw, int inW, int inH, const IspFrameBufs& B,
-                void* out);
+                void* out, int stopAfter = 0);
 
 }  // namespace s360
 
@@ -97,6 +99,13 @@ void isp_init(s360_isp* o, int device, const s360_isp_config& cfg);
 void isp_process(s360_isp* o, const uint16_t* raw16, int w, int h, void* out);
 void isp_process_packed(s360_isp* o, const uint8_t* frame, int bits, int w, int h, void* out);
 void isp_pipe_generated(s360_isp* o, const s360_camera_isp_gen_args& a);
+// s360_debug_isp_stages (include/s360_debug_isp.h): isp_process's upload and launch sequence, then the surviving buffers
+struct IspStageOut {
+  float *plane, *gv, *gh, *green, *tone, *low;
+  unsigned char* flag;
+  void* out;
+};
+void isp_debug_stages(s360_isp* o, const uint16_t* raw16, int inW, int inH, int stopAfter, const IspStageOut& S);
 // The first half of isp_process / isp_process_packed: upload and kernels enqueued on the object's own stream, nothing waits; the
 // result (B,G,R, 8 or 16 bit) is left on the device and returned. `what` names the entry point in a refusal.
 const void* isp_develop(s360_isp* o, const char* what, const uint16_t* raw16, int inW, int inH);

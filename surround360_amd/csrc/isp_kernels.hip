@@ -542,7 +542,7 @@ __global__ __launch_bounds__(256) void k_isp_finish(const float* __restrict__ im
 
 // ======================================================================================================================
 void isp_launch(hipStream_t st, const IspDev& d, const unsigned short* raw, int inW, int inH, const IspFrameBufs& B,
-                void* out) {
+                void* out, int stopAfter) {
   const int w = inW / d.resize, h = inH / d.resize;
   const size_t n = (size_t)w * h;
   const dim3 row(256), grd((w + 255) / 256, h);
@@ -569,6 +569,7 @@ void isp_launch(hipStream_t st, const IspDev& d, const unsigned short* raw, int 
     const dim3 gr((h + IR_ROWS - 1) / IR_ROWS), gc((w * 3 + 63) / 64);
     hipLaunchKernelGGL((k_isp_iir_rows_t<false, false>), gr, dim3(64), 0, st, B.img, B.scratch, B.state, w, h, d.alpha, d.maxVal);
     hipLaunchKernelGGL((k_isp_iir_rows_t<true, false>), gr, dim3(64), 0, st, B.scratch, B.lp, B.state, w, h, d.alpha, d.maxVal);
+    if (stopAfter == 1) return;  // (test tap: lp holds the row direction's result)
     hipLaunchKernelGGL((k_isp_iir_cols_t<false, false>), gc, dim3(64), 0, st, B.lp, B.scratch, B.state, w, h, d.alpha, d.maxVal);
     hipLaunchKernelGGL((k_isp_iir_cols_t<true, false>), gc, dim3(64), 0, st, B.scratch, B.lp, B.state, w, h, d.alpha, d.maxVal);
     if (d.outputBpp == 8)
@@ -590,9 +591,12 @@ void isp_launch(hipStream_t st, const IspDev& d, const unsigned short* raw, int 
 // ======================================================================================================================
 // The ACCELERATED ISP's arithmetic: CameraIspPipe (camera_isp/CameraIspPipe.h), i.e. the Halide pipeline that
 // camera_isp/CameraIspGen.cpp generates — what the reference's Unpacker always runs (Unpacker.cpp:24,176-183) and Raw2Rgb runs
-// with --accelerate (Raw2Rgb.cpp:427-440). Written from the generator's source, function by function; Halide cannot be built
-// here, so this arithmetic is NOT pinned against the reference (include/s360.h and DESIGN.md section 8 say what may differ at
-// rounding level). Same structure as the soft ISP above, other details: the image is extended by mirroring WITHOUT boundary
+// with --accelerate (Raw2Rgb.cpp:427-440). Written from the generator's source, function by function, and PINNED since round 5:
+// the tests' CPU restatement of the pipeline, which these kernels equal bit for bit in the output and in every float intermediate
+// (tests/test_gpu_isp.py, tests/test_gpu_isp_stages.py), equals the generator itself executed over an evaluator of the Halide
+// front end (tests/test_cpu_isp.py). Halide itself cannot be built here: include/s360.h and DESIGN.md section 8 say which choices
+// a real Halide build may make differently at rounding level.
+// Same structure as the soft ISP above, other details: the image is extended by mirroring WITHOUT boundary
 // logic in the stencils — the site plane is computed for 8 pixels beyond every edge (raw: mirror_interior, vignette tables:
 // mirror_image, site colour from the virtual coordinate: CameraIspGen.cpp:674-680), the flags for 6, green for 2 —; black
 // level, white balance and clamp are one A (x - B); the horizontal vignette table has its green and blue columns swapped
@@ -770,7 +774,7 @@ __global__ __launch_bounds__(256) void k_pipe_finish(const float* __restrict__ t
 }
 
 void isp_pipe_launch(hipStream_t st, const IspPipeDev& d, const unsigned short* raw, int w, int h, const IspPipeBufs& B,
-                     void* out) {
+                     void* out, int stopAfter) {
   const size_t n = (size_t)w * h;
   const dim3 row(256);
   if (d.fast) hipLaunchKernelGGL((k_pipe_site<true>), dim3((w + 2 * PP + 255) / 256, h + 2 * PP), row, 0, st, raw, w, h, d, B.vigH, B.vigV, B.site);
@@ -791,6 +795,7 @@ void isp_pipe_launch(hipStream_t st, const IspPipeDev& d, const unsigned short* 
   const dim3 gr((h + IR_ROWS - 1) / IR_ROWS), gc((w * 3 + 63) / 64);
   hipLaunchKernelGGL((k_isp_iir_cols_t<false, true>), gc, dim3(64), 0, st, B.tone, B.scratch, B.state, w, h, d.alpha, d.maxVal);
   hipLaunchKernelGGL((k_isp_iir_cols_t<true, true>), gc, dim3(64), 0, st, B.scratch, B.low, B.state, w, h, d.alpha, d.maxVal);
+  if (stopAfter == 1) return;  // (test tap: low holds the y direction's result)
   hipLaunchKernelGGL((k_isp_iir_rows_t<false, true>), gr, dim3(64), 0, st, B.low, B.scratch, B.state, w, h, d.alpha, d.maxVal);
   hipLaunchKernelGGL((k_isp_iir_rows_t<true, true>), gr, dim3(64), 0, st, B.scratch, B.low, B.state, w, h, d.alpha, d.maxVal);
   if (d.outputBpp == 8) hipLaunchKernelGGL((k_pipe_finish<false, unsigned char>), dim3(gp), row, 0, st, B.tone, B.low, n, d, B.exptab, (unsigned char*)out);

@@ -3,7 +3,8 @@
   CameraIsp(json, output_bpp) + the Raw2Rgb flags     SR/camera_isp/CameraIsp.h:425-607, Raw2Rgb.cpp:25-39, 441-456
   load_image + get_image                              CameraIsp.h:831-854, 1275-1299
   CameraIspPipe(json, fast, output_bpp)               SR/camera_isp/CameraIspPipe.h (pipe=PIPE / PIPE_FAST: the Halide
-                                                      pipeline's arithmetic restated from CameraIspGen.cpp, not pinned)
+                                                      pipeline's arithmetic restated from CameraIspGen.cpp and pinned to
+                                                      that generator executed: tests/test_cpu_isp.py)
 
 Everything computes on the GPU; numpy arrays stand in for cv::Mat (H x W uint16 raw, H x W x 3 BGR out)."""
 import ctypes as C
@@ -93,6 +94,36 @@ class CameraIsp:
         check(lib().s360_isp_process_packed_png(self.h, fr.ctypes.data_as(C.c_void_p), bits, w, h, out.ctypes.data_as(C.c_void_p),
                                                 C.c_size_t(out.size), C.byref(n)))
         return out[:n.value]
+
+    def debug_stages(self, raw16, stop_after=0):
+        """Test tap (include/s360_debug_isp.h): get_image's launch sequence, then the device buffers it leaves behind:
+        (out, {stage: array}). Soft ISP: plane, tone, with demosaic_filter 2 flag, gV, gH, green (all H x W of the output), with
+        sharpening low. Pipeline: plane (H + 16) x (W + 16), tone, and unless fast flag (+12), green (+4), low. stop_after=1 ends the
+        sequence after the low pass's first direction: the dictionary then holds that as low_first instead of low, and out is None."""
+        raw = np.ascontiguousarray(raw16, np.uint16)
+        hh, ww = raw.shape
+        c = self.config
+        h, w = hh // c.resize, ww // c.resize
+        pipe, fast = c.pipe != SOFT, c.pipe == PIPE_FAST
+        vote = not fast if pipe else c.demosaic_filter == EDGE_AWARE_DM_FILTER
+        low = not fast if pipe else all(c.sharpening[k] != 0.0 for k in range(3))
+        f = np.float32
+        st = {"plane": np.empty((h + 16, w + 16) if pipe else (h, w), f), "tone": np.empty((h, w, 3), f)}
+        if vote:
+            st["flag"] = np.empty((h + 12, w + 12) if pipe else (h, w), np.uint8)
+            st["green"] = np.empty((h + 4, w + 4) if pipe else (h, w), f)
+            if not pipe:
+                st["gV"], st["gH"] = np.empty((h, w), f), np.empty((h, w), f)
+        low_name = "low_first" if stop_after else "low"
+        if low:
+            st[low_name] = np.empty((h, w, 3), f)
+        out = None if stop_after else np.empty((h, w, 3), np.uint8 if c.output_bpp == 8 else np.uint16)
+
+        def p(a):
+            return a.ctypes.data_as(C.c_void_p) if a is not None else None
+        check(lib().s360_debug_isp_stages(self.h, p(raw), ww, hh, int(stop_after), p(st["plane"]), p(st.get("flag")), p(st.get("gV")),
+                                          p(st.get("gH")), p(st.get("green")), p(st["tone"]), p(st.get(low_name)), p(out)))
+        return out, st
 
     def close(self):
         if self.h:

@@ -219,8 +219,11 @@ def sharpen(bgr, amount):
 
 
 # ---- coverage counters (oracle/cvlite.h: CoverageCounter, in that order) -----------------------------------------
+ISP_COVERAGE_NAMES = ("flag_tie", "vote_39", "vote_40", "clamp_lo", "clamp_hi", "raw_ge_one", "lut_first", "lut_last", "core_zero",
+                      "core_saturated", "out_at_max", "iir_clamped")
+PIPE_COVERAGE_NAMES = tuple(n for n in ISP_COVERAGE_NAMES if n not in ("raw_ge_one", "iir_clamped"))  # (the pipeline has neither)
 COVERAGE_NAMES = ("tiny_operand", "tie_rejected", "alpha_at_threshold", "median_signed_zeros", "search_tie",
-                  "search_nonfinite")
+                  "search_nonfinite") + tuple("isp_" + n for n in ISP_COVERAGE_NAMES) + tuple("pipe_" + n for n in PIPE_COVERAGE_NAMES)
 
 
 def coverage_reset():
@@ -519,6 +522,47 @@ def isp_pipe_run(cfg, raw, fast=False):
     if lib().orc_isp_pipe_run(C.byref(cfg), int(bool(fast)), _p(raw), raw.shape[1], raw.shape[0], _p(out), err, 256) != 0:
         raise RuntimeError(err.value.decode())
     return out
+
+
+def isp_run_stages(cfg, raw):
+    """isp_run plus the intermediates of the same computation (oracle/isp.h: IspStages): (out, {stage: array}). plane, flag, gV, gH,
+    green: H x W of the output; tone, low_first (the low pass after the row direction), low: H x W x 3. Stages the configuration
+    does not have (flag .. green without the edge-aware demosaic, the low passes without sharpening) are absent."""
+    raw = np.ascontiguousarray(raw, np.uint16)
+    assert lib().orc_isp_config_size() == C.sizeof(IspConfigC)
+    out = _isp_out(raw, cfg)
+    h, w = out.shape[:2]
+    st = {"plane": np.zeros((h, w), np.float32), "tone": np.zeros((h, w, 3), np.float32)}
+    if cfg.demosaicFilter == 2:
+        st.update(flag=np.zeros((h, w), np.uint8), gV=np.zeros((h, w), np.float32), gH=np.zeros((h, w), np.float32),
+                  green=np.zeros((h, w), np.float32))
+    if all(cfg.sharpening[k] != 0.0 for k in range(3)):
+        st.update(low_first=np.zeros((h, w, 3), np.float32), low=np.zeros((h, w, 3), np.float32))
+    err = C.create_string_buffer(256)
+    if lib().orc_isp_run_stages(C.byref(cfg), _p(raw), raw.shape[1], raw.shape[0], _p(out), _p(st["plane"]), _p(st.get("flag")),
+                                _p(st.get("gV")), _p(st.get("gH")), _p(st.get("green")), _p(st["tone"]), _p(st.get("low_first")),
+                                _p(st.get("low")), err, 256) != 0:
+        raise RuntimeError(err.value.decode())
+    return out, st
+
+
+def isp_pipe_run_stages(cfg, raw, fast=False):
+    """isp_pipe_run plus its intermediates (oracle/isp_pipe.h: IspPipeStages): (out, {stage: array}). plane: the site plane on the
+    image extended by 8, (H + 16) x (W + 16); flag: extended by 6; green: extended by 2; tone, low_first (after the y direction),
+    low: H x W x 3. The fast variant has plane and tone only."""
+    raw = np.ascontiguousarray(raw, np.uint16)
+    assert lib().orc_isp_config_size() == C.sizeof(IspConfigC)
+    h, w = raw.shape
+    out = np.zeros((h, w, 3), np.uint8 if cfg.outputBpp == 8 else np.uint16)
+    st = {"plane": np.zeros((h + 16, w + 16), np.float32), "tone": np.zeros((h, w, 3), np.float32)}
+    if not fast:
+        st.update(flag=np.zeros((h + 12, w + 12), np.uint8), green=np.zeros((h + 4, w + 4), np.float32),
+                  low_first=np.zeros((h, w, 3), np.float32), low=np.zeros((h, w, 3), np.float32))
+    err = C.create_string_buffer(256)
+    if lib().orc_isp_pipe_run_stages(C.byref(cfg), int(bool(fast)), _p(raw), w, h, _p(out), _p(st["plane"]), _p(st.get("flag")),
+                                     _p(st.get("green")), _p(st["tone"]), _p(st.get("low_first")), _p(st.get("low")), err, 256) != 0:
+        raise RuntimeError(err.value.decode())
+    return out, st
 
 
 def isp_tables(cfg):

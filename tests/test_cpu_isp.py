@@ -354,3 +354,149 @@ def test_packed_path_emulated_on_cpu(oracle, s360lib):
         raw16 = oracle.isp_unpack_frame(frame, bits, w, h)
         want = oracle.isp_run(oracle.isp_config_from_json(isputil.CONFIG_GRBG_NOSHARP, 16), raw16)
         assert np.array_equal(got, want), bits
+
+
+# ---- the edge cases of tests/isp_edge_cases.py: the oracle's outputs pinned, its stage taps checked ------------------------------------
+import isp_edge_cases as E  # noqa: E402
+
+EDGE_GROUPS = E.groups()
+EDGE_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "isp_edge_digests.json")
+
+
+@pytest.mark.parametrize("group", list(EDGE_GROUPS), ids=list(EDGE_GROUPS))
+def test_edge_cases_equal_compiled_reference(ref, refpipe, group):
+    """The oracle at the shapes and on the content tests/test_gpu_isp_stages.py holds the kernels to — minimum sizes, tile and batch
+    edges, resize of non-multiples, stuck-pixel removal at 8 x 8, flat / full-scale / Nyquist / noise content — against the
+    reference's own CameraIsp.h compiled and its generator executed."""
+    for case in EDGE_GROUPS[group]:
+        got, want = E.oracle_output(ref, case), E.reference_output(ref, case)
+        assert got.shape == want.shape and got.dtype == want.dtype, case.id
+        assert np.array_equal(got, want), "%s: %d of %d samples differ" % (case.id, (got != want).sum(), got.size)
+
+
+@pytest.mark.parametrize("group", list(EDGE_GROUPS), ids=list(EDGE_GROUPS))
+def test_edge_cases_equal_committed_digests(oracle, group):
+    """The same where the reference is absent: digests of the reference libraries' outputs, committed by
+    tests/golden/make_isp_edge_golden.py."""
+    import json
+    golden = json.load(open(EDGE_DIGESTS))
+    assert sorted(golden) == sorted(c.id for c in E.all_cases())
+    for case in EDGE_GROUPS[group]:
+        assert E.digest(E.oracle_output(oracle, case)) == golden[case.id], case.id
+
+
+def test_edge_content_reaches_its_counters(oracle):
+    """Every content case makes the coverage counters it names non-zero, and together they name every ISP counter."""
+    named = set()
+    for case in E.all_cases():
+        if not case.counters:
+            continue
+        cfg = oracle.isp_config_from_json(E.json_of(case), case.bpp, case.dm, case.resize)
+        with oracle.coverage() as cov:
+            (oracle.isp_pipe_run if case.pipe else oracle.isp_run)(cfg, E.raw_of(case))
+        prefix = "pipe_" if case.pipe else "isp_"
+        for name in case.counters:
+            assert cov.counts[prefix + name] > 0, (case.id, name)
+            named.add(prefix + name)
+    assert named == {n for n in oracle.COVERAGE_NAMES if n.startswith(("isp_", "pipe_"))}
+
+
+_f = np.float32
+
+
+def _expf(x):
+    return np.exp(x.astype(np.float64)).astype(np.float32)  # (correctly rounded, as the C library's expf is on these operands)
+
+
+def _iir(a, alpha, axis, soft, max_val):
+    """The low pass along one axis of an H x W x 3 float32 image, restated with numpy scalars' rounding: the soft ISP's (reflected
+    chain ends, anticausal results clamped) or the pipeline's (the first element stays, nothing clamped)."""
+    a = np.moveaxis(a.copy(), axis, 0)
+    n, ia = a.shape[0], _f(1) - alpha
+    refl = lambda i: -i if i < 0 else 2 * n - i - 2 if i >= n else i  # noqa: E731
+    if soft:
+        v, buf, out = a[0].copy(), np.empty_like(a), np.empty_like(a)
+        for j in range(1, n + 1):
+            v = a[refl(j)] * ia + v * alpha
+            buf[refl(j - 1)] = v
+        for j in range(n - 2, -2, -1):
+            v = buf[refl(j)] * ia + v * alpha
+            out[j + 1] = np.clip(v, _f(0), max_val)
+    else:
+        out = a
+        for i in range(1, n):
+            out[i] = out[i - 1] * alpha + out[i] * ia
+        for i in range(n - 2, -1, -1):
+            out[i] = out[i + 1] * alpha + out[i] * ia
+    return np.moveaxis(out, 0, axis)
+
+
+def _votes(flag, pad_mode):
+    """9 x 9 sums of a flag plane: over the image with reflected borders (soft ISP), or over an already extended plane."""
+    f = np.pad(flag.astype(np.int32), 4, mode="reflect") if pad_mode else flag.astype(np.int32)
+    h, w = f.shape[0] - 8, f.shape[1] - 8
+    return sum(f[dy:dy + h, dx:dx + w] for dy in range(9) for dx in range(9))
+
+
+def test_soft_stage_taps_reproduce_the_output(oracle):
+    """The planes isp_run_stages hands out are the ones the output is made of: the remaining steps applied to them in numpy
+    (float32 operation by operation) give the oracle's own output, and each plane follows from the one before it."""
+    import json
+    case = [c for c in EDGE_GROUPS["soft-dm2-full-bpp16-shapes"] if (c.w, c.h) == (65, 22)][0]
+    cfg = oracle.isp_config_from_json(E.json_of(case), 16, 2, 1)
+    out, st = oracle.isp_run_stages(cfg, E.raw_of(case))
+    assert np.array_equal(out, oracle.isp_run(cfg, E.raw_of(case)))
+    h, w = st["plane"].shape
+    yy, xx = np.mgrid[0:h, 0:w]
+    green_site = (xx + yy) % 2 == 1  # RGGB
+    for name in ("gV", "gH", "green"):  # a green site keeps its sample
+        assert np.array_equal(st[name][green_site], st["plane"][green_site]), name
+    pick = np.where(_votes(st["flag"], True) < 40, st["gV"], st["gH"])
+    assert np.array_equal(st["green"].view(np.uint32), pick.view(np.uint32))
+    assert 0 < st["flag"].mean() < 1 and not np.array_equal(st["gV"], st["gH"])
+    j = json.loads(E.json_of(case))["CameraIsp"]
+    alpha = np.power(_f(j["sharpeningSupport"]), _f(0.25), dtype=np.float32)
+    assert alpha == _f(float(_f(j["sharpeningSupport"])) ** 0.25)
+    max_val = _f(65535)
+    first = _iir(st["tone"], alpha, 1, True, max_val)
+    assert np.array_equal(first.view(np.uint32), st["low_first"].view(np.uint32))
+    low = _iir(st["low_first"], alpha, 0, True, max_val)
+    assert np.array_equal(low.view(np.uint32), st["low"].view(np.uint32))
+    hp = st["tone"] - st["low"]
+    ng = _f(1) - _expf(-((hp * hp) * _f(j["noiseCore"])))
+    amount = _f(1) + np.array(j["sharpening"], np.float32)
+    v = np.clip(st["low"] + hp * ng * amount, _f(0), max_val)
+    assert np.array_equal(v.astype(np.int32).astype(np.uint16)[:, :, ::-1], out)
+
+
+def test_pipe_stage_taps_reproduce_the_output(oracle):
+    """The same for isp_pipe_run_stages: green from the site plane and the flags, the low pass from the tone image, the output from
+    both."""
+    import json
+    case = [c for c in EDGE_GROUPS["pipe-full-bpp16-shapes"] if (c.w, c.h) == (65, 22)][0]
+    cfg = oracle.isp_config_from_json(E.json_of(case), 16, 2, 1)
+    out, st = oracle.isp_pipe_run_stages(cfg, E.raw_of(case))
+    assert np.array_equal(out, oracle.isp_pipe_run(cfg, E.raw_of(case)))
+    h, w = out.shape[:2]
+    s = st["plane"]
+    assert s.shape == (h + 16, w + 16) and st["flag"].shape == (h + 12, w + 12) and st["green"].shape == (h + 4, w + 4)
+    win = lambda dx, dy: s[6 + dy:6 + dy + h + 4, 6 + dx:6 + dx + w + 4]  # noqa: E731  (the site plane over green's area, shifted)
+    half, quarter = _f(0.5), _f(0.25)
+    gv = (win(0, 1) + win(0, -1)) * half + (_f(2) * win(0, 0) - win(0, 2) - win(0, -2)) * quarter
+    gh = (win(1, 0) + win(-1, 0)) * half + (_f(2) * win(0, 0) - win(2, 0) - win(-2, 0)) * quarter
+    yy, xx = np.mgrid[-2:h + 2, -2:w + 2]
+    green_site = (xx + yy) % 2 != 0  # RGGB: green where x and y differ in parity
+    want = np.where(green_site, win(0, 0), np.where(_votes(st["flag"], False) < 40, gv, gh))
+    assert np.array_equal(want.view(np.uint32), st["green"].view(np.uint32))
+    assert 0 < st["flag"].mean() < 1
+    j = json.loads(E.json_of(case))["CameraIsp"]
+    alpha = np.power(_f(j["sharpeningSupport"]), _f(0.25), dtype=np.float32)
+    first = _iir(st["tone"], alpha, 0, False, None)
+    assert np.array_equal(first.view(np.uint32), st["low_first"].view(np.uint32))
+    low = _iir(st["low_first"], alpha, 1, False, None)
+    assert np.array_equal(low.view(np.uint32), st["low"].view(np.uint32))
+    hp = st["tone"] - st["low"]
+    ng = _f(1) - _expf(-(hp * hp * _f(j["noiseCore"])))
+    amount = _f(1) + np.array(j["sharpening"], np.float32)
+    v = np.clip(st["low"][:, :, ::-1] + hp[:, :, ::-1] * ng * amount[::-1], _f(0), _f(65535))  # (the noise gain is read unswizzled)
+    assert np.array_equal(v.astype(np.int32).astype(np.uint16), out)
