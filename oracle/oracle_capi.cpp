@@ -218,6 +218,34 @@ void orc_pixflow_level(const float* I0, const float* I1, const float* a0, const 
                                     flow, hint);
   std::memcpy(flow_inout, flow.d.data(), flow.bytes());
 }
+// ... and the same level handing out its intermediates (pixflow.h: LevelStages). flow_in nullable: the coarsest level's path (zeros,
+// adjustInitialFlow with search20 and a hint). Every output pointer may be null: gradients I0x, I0y, I1x, I1y (w x h each), the
+// flow the blur reads, blurredFlow, the update mask (bytes), the flow after the forward sweep, the first median, the backward
+// sweep, the second median and lowAlphaFlowDiffusion (w x h x 2 each). prev_flow (w x h x 2) and motion (w x h), both or neither:
+// adjustFlowTowardPrevious as computeOpticalFlow applies it to a level — the previous flow times prev_scale, then the blend —
+// into `adjusted`.
+void orc_pixflow_level_stages(const float* I0, const float* I1, const float* a0, const float* a1, int w, int h, const float* flow_in,
+                              int hint, int search20, const float* prev_flow, const float* motion, float prev_scale, float* I0x,
+                              float* I0y, float* I1x, float* I1y, float* initial_flow, float* blurred_flow, uint8_t* updated,
+                              float* sweep_forward, float* median_first, float* sweep_backward, float* median_second,
+                              float* diffused, float* adjusted) {
+  PixFlowParams fp;
+  if (search20) fp.maxPercentage = 20;
+  PixFlow pf(fp);
+  PixFlow::LevelStages s;
+  ImgF flow = flow_in ? wrapF(flow_in, w, h, 2) : ImgF();
+  pf.patchMatchPropagationAndSearch(wrapF(I0, w, h, 1), wrapF(I1, w, h, 1), wrapF(a0, w, h, 1), wrapF(a1, w, h, 1), flow, hint, &s);
+  auto put = [](float* dst, const ImgF& i) { if (dst) std::memcpy(dst, i.d.data(), i.bytes()); };
+  put(I0x, s.I0x); put(I0y, s.I0y); put(I1x, s.I1x); put(I1y, s.I1y);
+  put(initial_flow, s.initialFlow); put(blurred_flow, s.blurredFlow);
+  if (updated) std::memcpy(updated, s.updated.data(), s.updated.size());
+  put(sweep_forward, s.sweepForward); put(median_first, s.medianFirst); put(sweep_backward, s.sweepBackward);
+  put(median_second, s.medianSecond); put(diffused, s.diffused);
+  if (prev_flow && motion && adjusted) {
+    PixFlow::adjustFlowTowardPrevious(wrapF(prev_flow, w, h, 2), wrapF(motion, w, h, 1), prev_scale, flow);
+    put(adjusted, flow);
+  }
+}
 
 // ---- geometry ----------------------------------------------------------------
 void orc_camera_rotation(const orc_camera_c* c, double* R9) {

@@ -62,6 +62,15 @@ struct PixFlow {
   };
   Debug* dbg = nullptr;
 
+  // Optional capture of ONE level's intermediates (orc_pixflow_level_stages), for stage-by-stage parity tests of the level's kernels
+  struct LevelStages {
+    ImgF I0x, I0y, I1x, I1y;
+    ImgF initialFlow;               // the flow the 15x15 blur reads: the caller's, or zeros after adjustInitialFlow
+    ImgF blurredFlow;
+    std::vector<uint8_t> updated;   // alpha0 > kUpdateAlphaThreshold && alpha1 > kUpdateAlphaThreshold, per pixel
+    ImgF sweepForward, medianFirst, sweepBackward, medianSecond, diffused;
+  };
+
   // PixFlow.h:477-491
   std::vector<ImgF> buildPyramid(const ImgF& src) const {
     std::vector<ImgF> pyr;
@@ -252,7 +261,7 @@ struct PixFlow {
 
   // PixFlow.h:344-413
   void patchMatchPropagationAndSearch(const ImgF& I0, const ImgF& I1, const ImgF& alpha0, const ImgF& alpha1,
-                                      ImgF& flow, int hint) const {
+                                      ImgF& flow, int hint, LevelStages* cap = nullptr) const {
     Level L;
     L.I0 = &I0; L.I1 = &I1; L.alpha0 = &alpha0; L.alpha1 = &alpha1;
     L.I0x = gaussianBlurF32(sobelX(I0), kGradientBlurKernelWidth, kGradientBlurSigma);
@@ -263,18 +272,43 @@ struct PixFlow {
       flow = ImgF(I0.w, I0.h, 2, 0.f);
       if (P.maxPercentage > 0 && hint != HINT_UNKNOWN) adjustInitialFlow(I0, I1, alpha0, alpha1, flow, hint);
     }
+    if (cap) cap->initialFlow = flow;
     L.blurredFlow = gaussianBlurF32(flow, kBlurredFlowKernelWidth, kBlurredFlowSigma);
     const int w = I0.w, h = I0.h;
+    if (cap) {
+      cap->I0x = L.I0x; cap->I0y = L.I0y; cap->I1x = L.I1x; cap->I1y = L.I1y;
+      cap->blurredFlow = L.blurredFlow;
+      cap->updated.resize(size_t(w) * h);
+      for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x)
+          cap->updated[size_t(y) * w + x] = alpha0.at(y, x) > kUpdateAlphaThreshold && alpha1.at(y, x) > kUpdateAlphaThreshold;
+    }
     for (int y = 0; y < h; ++y)
       for (int x = 0; x < w; ++x)
         if (alpha0.at(y, x) == kUpdateAlphaThreshold || alpha1.at(y, x) == kUpdateAlphaThreshold) coverageHit(COV_ALPHA_AT_THRESHOLD);
     for (int y = 0; y < h; ++y)
       for (int x = 0; x < w; ++x) sweepPixel(L, flow, x, y, +1);
+    if (cap) cap->sweepForward = flow;
     flow = medianBlur5(flow);
+    if (cap) cap->medianFirst = flow;
     for (int y = h - 1; y >= 0; --y)
       for (int x = w - 1; x >= 0; --x) sweepPixel(L, flow, x, y, -1);
+    if (cap) cap->sweepBackward = flow;
     flow = medianBlur5(flow);
+    if (cap) cap->medianSecond = flow;
     lowAlphaFlowDiffusion(alpha0, alpha1, flow);
+    if (cap) cap->diffused = flow;
+  }
+
+  // adjustFlowTowardPrevious (PixFlow.h:185-193) with the previous flow's level rescaled first (:147-153), as
+  // computeOpticalFlow applies them to a level
+  static void adjustFlowTowardPrevious(ImgF pf, const ImgF& mo, float prevScale, ImgF& flow) {
+    for (float& v : pf.d) v *= prevScale;
+    for (int y = 0; y < flow.h; ++y)
+      for (int x = 0; x < flow.w; ++x) {
+        const float w = 1.0f - mo.at(y, x);
+        for (int k = 0; k < 2; ++k) flow.at(y, x, k) = flow.at(y, x, k) * (1.0f - w) + pf.at(y, x, k) * w;
+      }
   }
 
   // PixFlow.h:81-183. prevFlow/prevI0/prevI1 may be empty (first frame / photo).

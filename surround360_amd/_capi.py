@@ -111,6 +111,18 @@ DEBUG_FINAL_FLOW_SYMBOLS = ["s360_debug_upscale_blur"]
 # ... and the one include/s360_debug_isp.h declares
 DEBUG_ISP_SYMBOLS = ["s360_debug_isp_stages"]
 
+# ... and the one include/s360_debug_flow_level.h declares
+DEBUG_FLOW_LEVEL_SYMBOLS = ["s360_debug_flow_level"]
+FLOW_LEVEL_INFO = ("lanes_per_pixel", "bands", "waves", "fast_division", "median_tile", "sweep_error")  # S360_FLI_*
+FLOW_LEVEL_INFO_COUNT = 8
+
+
+class FlowLevelOut(C.Structure):
+    """s360_flow_level_out (include/s360_debug_flow_level.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("gradients", "initial_flow", "blurred_flow", "updated", "row_flags", "sweep_forward",
+                                          "median_first", "sweep_backward", "median_second", "diffused", "final_flow")]
+
+
 _lib = None
 
 
@@ -182,6 +194,10 @@ def lib():
                                                   C.POINTER(C.c_size_t)]
         L.s360_debug_isp_stages.restype = C.c_int
         L.s360_debug_isp_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8
+        L.s360_debug_flow_level.restype = C.c_int
+        L.s360_debug_flow_level.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                            C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(FlowLevelOut),
+                                            C.c_void_p]
         L.s360_isp_config_defaults.restype = None
         L.s360_isp_destroy.restype = None
         L.s360_isp_destroy.argtypes = [C.c_void_p]

@@ -11,6 +11,7 @@
 #include "../../include/s360.h"
 #include "../../include/s360_debug.h"
 #include "../../include/s360_debug_final_flow.h"
+#include "../../include/s360_debug_flow_level.h"
 #include "../../include/s360_debug_isp.h"
 #include "ctx.hpp"
 #include "isp.hpp"
@@ -521,6 +522,32 @@ int s360_debug_upscale_blur(s360_ctx* c, const float* src, int sw, int sh, int b
                         c->op_d.as<float*>(), generic != 0);
     for (size_t b = 0; b < B; ++b) d2h(c, out + 2 * nd * b, outs[b].p, nd * sizeof(float2));
     if (tiled) *tiled = (!generic && upscale_blur_tiled_fits(sw, sh, dw, dh)) ? 1 : 0;
+  });
+}
+// test tap (include/s360_debug_flow_level.h): one pyramid level of the flow engine on caller-made planes, stage by stage
+int s360_debug_flow_level(s360_ctx* c, const float* gray, const float* alpha, int n_images, int w, int h, const int* i0, const int* i1,
+                          int n_flows, const float* initial_flow, const char* alg, int hint, const float* prev_flow, const float* motion,
+                          float prev_scale, const s360_flow_level_out* out, int* info) {
+  static_assert(S360_FLI_COUNT == kFlowLevelInfoCount, "info block");
+  return guard(c, [&] {
+    need(c && gray && alpha && i0 && i1 && alg, "null argument");
+    need(w >= 2 && h >= 2, "level too small: the reference's bilinear taps need a 2x2 image (PixFlow.h:457-475)");
+    need(n_images >= 1 && n_flows >= 1 && n_flows <= kMaxFlows, "batch out of range");
+    need(hint >= 0 && hint <= 4, "bad direction hint");
+    for (int b = 0; b < n_flows; ++b)
+      need(i0[b] >= 0 && i0[b] < n_images && i1[b] >= 0 && i1[b] < n_images, "image index out of range");
+    need((prev_flow != nullptr) == (motion != nullptr), "previous flow and motion planes must be given together");
+    need(!(prev_flow && out && out->diffused), "with previous state the diffusion and the adjustment are one launch: no diffused flow");
+    const PixFlowConsts pc = pixflow_consts_by_name(alg);
+    FlowLevelTaps t;
+    if (out) {
+      t.gradients = out->gradients; t.initial_flow = out->initial_flow; t.blurred_flow = out->blurred_flow;
+      t.updated = out->updated; t.row_flags = out->row_flags; t.sweep_forward = out->sweep_forward;
+      t.median_first = out->median_first; t.sweep_backward = out->sweep_backward; t.median_second = out->median_second;
+      t.diffused = out->diffused; t.final_flow = out->final_flow;
+    }
+    c->flow->debug_level(c->st, pc, n_images, n_flows, w, h, gray, alpha, i0, i1, initial_flow, hint, prev_flow, motion, prev_scale, t,
+                         info);
   });
 }
 

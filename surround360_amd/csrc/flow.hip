@@ -125,32 +125,19 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
   M.G.ensure(N * n0 * sizeof(float2));
   M.flowA.ensure(B * n0 * sizeof(float2));
   M.flowB.ensure(B * n0 * sizeof(float2));
-  if (sweep_fast_ < 0) {
-    const char* d = std::getenv("S360_SWEEP_DIV");  // "ieee": IEEE division / sqrt expansions instead of the verified fast ones (same bits)
-    sweep_fast_ = !(d && std::string(d) == "ieee");
+  std::vector<float> divs;
+  divs.push_back(0.001f);
+  for (int l = 0; l < L; ++l) {
+    divs.push_back((float)lv_.w[l]);
+    divs.push_back((float)lv_.h[l]);
   }
-  bool fastOk = false;
-  if (sweep_fast_) {
-    std::vector<float> divs;
-    divs.push_back(0.001f);
-    for (int l = 0; l < L; ++l) {
-      divs.push_back((float)lv_.w[l]);
-      divs.push_back((float)lv_.h[l]);
-    }
-    fastOk = sweep_verify_divisors(st, divs);
-  }
+  const bool fastOk = sweeps_fast(st, divs);
   M.rec.ensure(B * n0 * (sweep_mode_ == 3 ? sizeof(float2) : sizeof(float4)));  // half-records / full records (flow_kernels.hpp)
   // Band hand-off granules + ticket counters of every sweep launch of this call (2 per level): one arena, reset to
   // all-ones ("not written") by ONE memset instead of one per launch.
-  auto handoff_bytes = [&](int l) {
-    const size_t b = sweep_mode_ == 3 ? sweep_quad_handoff_bytes(lv_.w[l], lv_.h[l], B)
-                                      : sweep_lock_handoff_bytes(lv_.w[l], lv_.h[l], B, sweep_lock_waves());
-    return (b + 255) & ~(size_t)255;
-  };
   // + per level one word per (flow, row): all-ones = no pixel of the row is updated (written by the record kernel)
-  auto rowflag_bytes = [&](int l) { return ((size_t)B * lv_.h[l] * sizeof(unsigned) + 255) & ~(size_t)255; };
   std::vector<size_t> hoff(L + 1, 0);
-  for (int l = 0; l < L; ++l) hoff[l + 1] = hoff[l] + 2 * handoff_bytes(l) + rowflag_bytes(l);
+  for (int l = 0; l < L; ++l) hoff[l + 1] = hoff[l] + 2 * handoff_bytes(lv_.w[l], lv_.h[l], B) + rowflag_bytes(lv_.h[l], B);
   M.handoff.ensure(hoff[L]);
   S360_HIP(hipMemsetAsync(M.handoff.p, 0xFF, hoff[L], st));
   if (!err_.p) {
@@ -161,8 +148,7 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
   auto LI = [&](int l) { return pyrI + (size_t)2 * N * lv_.off[l]; };
   auto LA = [&](int l) { return pyrI + (size_t)2 * N * lv_.off[l] + (size_t)N * lv_.w[l] * lv_.h[l]; };
 
-  const BlurTaps tPre = gaussian_taps(5, 0.25f), tGrad = gaussian_taps(3, 0.5f), tFlow = gaussian_taps(15, 8.0f),
-                 tFinal = gaussian_taps(3, 1.0f);
+  const BlurTaps tPre = gaussian_taps(5, 0.25f), tFinal = gaussian_taps(3, 1.0f);
   {
     ProfScope ps(P, "flow_entry");
     // the downscaled image itself is read again only by k_motion (temporal state): stored only then
@@ -210,52 +196,22 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
   for (int l = L - 1; l >= 0; --l) {
     const int wl = lv_.w[l], hl = lv_.h[l];
     const size_t nl = (size_t)wl * hl;
-    {
-      ProfScope ps(P, "flow_gradients");
-      launch_gradients(st, LI(l), M.G.as<float2>(), wl, hl, nl, N, tGrad);
-    }
-    if (l == L - 1) {
-      S360_HIP(hipMemsetAsync(cur, 0, B * nl * sizeof(float2), st));
-      if (pc.maxPercentage > 0 && hint != 0) {
-        ProfScope ps(P, "flow_search_init");
-        M.I1eq.ensure(B * nl * sizeof(float));
-        const int dist = (24 * pc.maxPercentage + 50) / 100;
-        launch_search_init(st, LI(l), LA(l), wl, hl, nl, B, idx, cur, hint, dist, M.I1eq.as<float>());
-      }
-    }
-    {
-      ProfScope ps(P, "flow_blur15");  // the blurred flow goes straight into the sweeps' half-records
-      launch_blur_to_records(st, cur, M.rec.p, wl, hl, nl, B, tFlow, sweep_mode_ == 3 ? nullptr : M.G.as<float2>(), LA(l), idx,
-                             reinterpret_cast<unsigned*>((char*)M.handoff.p + hoff[l] + 2 * handoff_bytes(l)));
-    }
-    auto sweep = [&](float2* fl, int dir) {
-      ProfScope ps(P, "flow_sweep");
-      void* ho = (char*)M.handoff.p + hoff[l] + (dir > 0 ? 0 : handoff_bytes(l));
-      if (sweep_mode_ == 3)
-        launch_sweep_quad(st, M.rec.as<float2>(), M.G.as<float2>(), fl, ho, err_.as<unsigned>(), wl, hl, nl, B, idx, dir, pc,
-                          fastOk, reinterpret_cast<const unsigned*>((char*)M.handoff.p + hoff[l] + 2 * handoff_bytes(l)));
-      else
-        launch_sweep_lock(st, M.rec.as<float4>(), M.G.as<float2>(), fl, ho, err_.as<unsigned>(), wl, hl, nl, B, idx, dir, pc,
-                          fastOk);
-    };
-    sweep(cur, +1);
-    {
-      ProfScope ps(P, "flow_median");
-      launch_median5_c2(st, cur, oth, wl, hl, nl, B);
-    }
-    sweep(oth, -1);
-    {
-      ProfScope ps(P, "flow_median");
-      launch_median5_c2(st, oth, cur, wl, hl, nl, B);
-    }
-    {
-      ProfScope ps(P, "flow_diffusion");
-      if (usePrev)  // ... and adjustFlowTowardPrevious in the same pass (the previous flow's level rescaled as it is read)
-        launch_diffusion_adjust(st, cur, oth, wl, hl, nl, B, tFlow, LA(l), idx, prevPyr + (size_t)B * lv_.off[l],
-                                motionPyr + (size_t)N * lv_.off[l], l == 0 ? 1.0f : float(lv_.h[l]) / float(lv_.h[0]));
-      else
-        launch_diffusion(st, cur, oth, wl, hl, nl, B, tFlow, LA(l), idx);
-    }
+    // (the rescale of the previous flow's level, PixFlow.h:147-153, is applied where it is read; level 0's factor is exactly 1)
+    FlowLevelArgs a;
+    a.w = wl; a.h = hl; a.N = N; a.B = B;
+    a.I = LI(l); a.A = LA(l);
+    a.idx = idx;
+    a.cur = cur; a.oth = oth;
+    a.first = l == L - 1;
+    a.hint = hint;
+    a.handoff_fwd = (char*)M.handoff.p + hoff[l];
+    a.handoff_bwd = (char*)M.handoff.p + hoff[l] + handoff_bytes(wl, hl, B);
+    a.rowflags = reinterpret_cast<unsigned*>((char*)M.handoff.p + hoff[l] + 2 * handoff_bytes(wl, hl, B));
+    a.fast = fastOk;
+    a.prev = usePrev ? prevPyr + (size_t)B * lv_.off[l] : nullptr;
+    a.motion = usePrev ? motionPyr + (size_t)N * lv_.off[l] : nullptr;
+    a.prev_scale = l == 0 ? 1.0f : float(lv_.h[l]) / float(lv_.h[0]);
+    level(st, pc, a);
     if (capture_levels) {
       std::vector<float> hbuf(B * nl * 2);
       S360_HIP(hipMemcpyAsync(hbuf.data(), oth, hbuf.size() * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -271,6 +227,179 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
       // final upscale + scalar + 3x3 blur fused: the upscaled flow is evaluated while the blur's tile is loaded
       launch_upscale_blur(st, oth, wl, hl, nl, nullptr, w, h, (size_t)w * h, B, 1.0f / pc.downscaleFactor, tFinal, outTab);
     }
+  }
+}
+
+size_t FlowEngine::handoff_bytes(int w, int h, int B) const {
+  const size_t b = sweep_mode_ == 3 ? sweep_quad_handoff_bytes(w, h, B) : sweep_lock_handoff_bytes(w, h, B, sweep_lock_waves());
+  return (b + 255) & ~(size_t)255;
+}
+
+bool FlowEngine::sweeps_fast(hipStream_t st, const std::vector<float>& divisors) {
+  if (sweep_fast_ < 0) {
+    const char* d = std::getenv("S360_SWEEP_DIV");  // "ieee": IEEE division / sqrt expansions instead of the verified fast ones (same bits)
+    sweep_fast_ = !(d && std::string(d) == "ieee");
+  }
+  return sweep_fast_ ? sweep_verify_divisors(st, divisors) : false;
+}
+
+void FlowEngine::level(hipStream_t st, const PixFlowConsts& pc, const FlowLevelArgs& a, const FlowLevelTaps* tap) {
+  Profiler& P = *prof_;
+  FlowBufs& M = *bufs_;
+  const int wl = a.w, hl = a.h, N = a.N, B = a.B;
+  const size_t nl = (size_t)wl * hl;
+  float2* const cur = a.cur;
+  float2* const oth = a.oth;
+  // (tests only) what a launch has left, copied to the host before the next one overwrites it
+  auto grab = [&](void* host, const void* dev, size_t bytes) {
+    if (!tap || !host) return;
+    S360_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+    S360_HIP(hipStreamSynchronize(st));
+  };
+  const size_t flowBytes = (size_t)B * nl * sizeof(float2);
+  {
+    ProfScope ps(P, "flow_gradients");
+    launch_gradients(st, a.I, M.G.as<float2>(), wl, hl, nl, N, tGrad_);
+  }
+  if (tap) grab(tap->gradients, M.G.p, (size_t)N * nl * sizeof(float2));
+  if (a.first) {
+    S360_HIP(hipMemsetAsync(cur, 0, B * nl * sizeof(float2), st));
+    if (pc.maxPercentage > 0 && a.hint != 0) {
+      ProfScope ps(P, "flow_search_init");
+      M.I1eq.ensure(B * nl * sizeof(float));
+      const int dist = (24 * pc.maxPercentage + 50) / 100;
+      launch_search_init(st, a.I, a.A, wl, hl, nl, B, a.idx, cur, a.hint, dist, M.I1eq.as<float>());
+    }
+  }
+  if (tap) grab(tap->initial_flow, cur, flowBytes);
+  {
+    ProfScope ps(P, "flow_blur15");  // the blurred flow goes straight into the sweeps' half-records
+    launch_blur_to_records(st, cur, M.rec.p, wl, hl, nl, B, tFlow_, sweep_mode_ == 3 ? nullptr : M.G.as<float2>(), a.A, a.idx,
+                           a.rowflags);
+  }
+  if (tap && (tap->blurred_flow || tap->updated)) {  // the records decoded: both formats mark a pixel that is not updated with a NaN first word
+    const size_t words = sweep_mode_ == 3 ? 2 : 4;
+    std::vector<float> rec((size_t)B * nl * words);
+    grab(rec.data(), M.rec.p, rec.size() * sizeof(float));
+    for (size_t i = 0; i < (size_t)B * nl; ++i) {
+      const float* r = &rec[i * words];
+      if (tap->updated) tap->updated[i] = r[0] == r[0] ? 1 : 0;
+      if (tap->blurred_flow) {
+        tap->blurred_flow[2 * i] = r[words - 2];
+        tap->blurred_flow[2 * i + 1] = r[words - 1];
+      }
+    }
+  }
+  if (tap) grab(tap->row_flags, a.rowflags, (size_t)B * hl * sizeof(unsigned));
+  auto sweep = [&](float2* fl, int dir) {
+    ProfScope ps(P, "flow_sweep");
+    void* ho = dir > 0 ? a.handoff_fwd : a.handoff_bwd;
+    if (sweep_mode_ == 3)
+      launch_sweep_quad(st, M.rec.as<float2>(), M.G.as<float2>(), fl, ho, err_.as<unsigned>(), wl, hl, nl, B, a.idx, dir, pc,
+                        a.fast, a.rowflags);
+    else
+      launch_sweep_lock(st, M.rec.as<float4>(), M.G.as<float2>(), fl, ho, err_.as<unsigned>(), wl, hl, nl, B, a.idx, dir, pc,
+                        a.fast);
+  };
+  sweep(cur, +1);
+  if (tap) grab(tap->sweep_forward, cur, flowBytes);
+  {
+    ProfScope ps(P, "flow_median");
+    launch_median5_c2(st, cur, oth, wl, hl, nl, B);
+  }
+  if (tap) grab(tap->median_first, oth, flowBytes);
+  sweep(oth, -1);
+  if (tap) grab(tap->sweep_backward, oth, flowBytes);
+  {
+    ProfScope ps(P, "flow_median");
+    launch_median5_c2(st, oth, cur, wl, hl, nl, B);
+  }
+  if (tap) grab(tap->median_second, cur, flowBytes);
+  {
+    ProfScope ps(P, "flow_diffusion");
+    if (a.prev)  // ... and adjustFlowTowardPrevious in the same pass (the previous flow's level rescaled as it is read)
+      launch_diffusion_adjust(st, cur, oth, wl, hl, nl, B, tFlow_, a.A, a.idx, a.prev, a.motion, a.prev_scale);
+    else
+      launch_diffusion(st, cur, oth, wl, hl, nl, B, tFlow_, a.A, a.idx);
+  }
+  if (tap) {
+    if (!a.prev) grab(tap->diffused, oth, flowBytes);
+    grab(tap->final_flow, oth, flowBytes);
+  }
+}
+
+void FlowEngine::debug_level(hipStream_t st, const PixFlowConsts& pc, int N, int B, int w, int h, const float* gray,
+                             const float* alpha, const int* i0, const int* i1, const float* init, int hint, const float* prev,
+                             const float* motion, float prev_scale, const FlowLevelTaps& taps, int* info) {
+  if (w < 2 || h < 2 || N < 1 || B < 1 || B > kMaxFlows) throw Error(-1, "FlowEngine: bad level");
+  if ((prev != nullptr) != (motion != nullptr)) throw Error(-1, "FlowEngine: previous-frame state must be complete or absent");
+  if (prev && taps.diffused) throw Error(-1, "FlowEngine: with previous state the diffusion and the adjustment are one launch");
+  FlowBatch fb;  // the index arrays take the way of a batch's: the pointer tables of this one stay unused
+  fb.images.assign(N, nullptr);
+  for (int b = 0; b < B; ++b) {
+    if (i0[b] < 0 || i0[b] >= N || i1[b] < 0 || i1[b] >= N) throw Error(-1, "FlowEngine: image index out of range");
+    fb.add_flow(i0[b], i1[b], nullptr);
+  }
+  FlowBufs& M = *bufs_;
+  const size_t nl = (size_t)w * h;
+  const unsigned long long* tab = batch_tables(st, fb);
+  FlowLevelArgs a;
+  a.w = w; a.h = h; a.N = N; a.B = B;
+  a.idx.i0 = reinterpret_cast<const int*>(tab + 2 * N + 2 * B);
+  a.idx.i1 = a.idx.i0 + B;
+  M.pyrI.ensure(2 * N * nl * sizeof(float));  // N grey planes, then N alpha planes, as a level of the pyramid lies
+  M.G.ensure(N * nl * sizeof(float2));
+  M.flowA.ensure(B * nl * sizeof(float2));
+  M.flowB.ensure(B * nl * sizeof(float2));
+  M.rec.ensure(B * nl * (sweep_mode_ == 3 ? sizeof(float2) : sizeof(float4)));
+  const size_t hb = handoff_bytes(w, h, B);
+  M.handoff.ensure(2 * hb + rowflag_bytes(h, B));
+  S360_HIP(hipMemsetAsync(M.handoff.p, 0xFF, 2 * hb + rowflag_bytes(h, B), st));
+  if (!err_.p) {
+    err_.ensure(sizeof(unsigned));
+    S360_HIP(hipMemsetAsync(err_.p, 0, sizeof(unsigned), st));
+  }
+  float* I = M.pyrI.as<float>();
+  S360_HIP(hipMemcpyAsync(I, gray, N * nl * sizeof(float), hipMemcpyHostToDevice, st));
+  S360_HIP(hipMemcpyAsync(I + N * nl, alpha, N * nl * sizeof(float), hipMemcpyHostToDevice, st));
+  a.I = I;
+  a.A = I + N * nl;
+  a.cur = M.flowA.as<float2>();
+  a.oth = M.flowB.as<float2>();
+  a.first = init == nullptr;
+  if (init) S360_HIP(hipMemcpyAsync(a.cur, init, B * nl * sizeof(float2), hipMemcpyHostToDevice, st));
+  a.hint = hint;
+  a.handoff_fwd = M.handoff.p;
+  a.handoff_bwd = (char*)M.handoff.p + hb;
+  a.rowflags = reinterpret_cast<unsigned*>((char*)M.handoff.p + 2 * hb);
+  a.fast = sweeps_fast(st, {0.001f, (float)w, (float)h});
+  a.prev = nullptr;
+  a.motion = nullptr;
+  a.prev_scale = prev_scale;
+  if (prev) {
+    M.prevPyr.ensure(B * nl * sizeof(float2));
+    M.motionPyr.ensure(N * nl * sizeof(float));
+    S360_HIP(hipMemcpyAsync(M.prevPyr.p, prev, B * nl * sizeof(float2), hipMemcpyHostToDevice, st));
+    S360_HIP(hipMemcpyAsync(M.motionPyr.p, motion, N * nl * sizeof(float), hipMemcpyHostToDevice, st));
+    a.prev = M.prevPyr.as<float2>();
+    a.motion = M.motionPyr.as<float>();
+  }
+  S360_HIP(hipStreamSynchronize(st));  // (the caller's buffers are pageable: the copies have read them by now)
+  level(st, pc, a, &taps);
+  S360_HIP(hipStreamSynchronize(st));
+  if (info) {
+    std::memset(info, 0, kFlowLevelInfoCount * sizeof(int));
+    if (sweep_mode_ == 3) {
+      info[0] = sweep_quad_lanes_per_pixel(h, B);
+      info[1] = sweep_quad_num_bands(h, B);
+      info[2] = sweep_quad_waves(h, B);
+    } else {
+      info[1] = sweep_lock_num_wgs(h, sweep_lock_waves());
+      info[2] = info[1] * B * (sweep_lock_waves() + 2);
+    }
+    info[3] = a.fast ? 1 : 0;
+    info[4] = median5_tile_bx(w, h);
+    info[5] = (int)take_error(st);
   }
 }
 

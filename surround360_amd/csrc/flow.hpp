@@ -50,6 +50,41 @@ struct FlowBufs {
   DevBuf down, prevdown, gray, pyrI, G, flowA, flowB, prevFlowDown, prevPyr, motionPyr, I1eq, rec, handoff;
 };
 
+// What one pyramid level works on (FlowEngine::level): the body of compute()'s level loop, which the test tap
+// s360_debug_flow_level (FlowEngine::debug_level) runs on planes of its own.
+struct FlowLevelArgs {
+  int w, h, N, B;
+  const float* I;      // N grey planes of the level, then ...
+  const float* A;      // ... N alpha planes
+  FlowIdx idx;
+  float2* cur;         // the flow entering the level (overwritten); ignored on entry when `first`
+  float2* oth;         // the level's result
+  bool first;          // the coarsest level: the flow starts as zeros, and as the search's result with pixflow_search_20 and a hint
+  int hint;
+  void* handoff_fwd;   // band hand-off arenas of the two sweeps and the row flags, all-ones on entry
+  void* handoff_bwd;
+  unsigned* rowflags;
+  bool fast;           // the sweeps' verified fast division
+  const float2* prev;  // previous flow's level (nullptr: no temporal state), the motion planes and the level's rescale factor
+  const float* motion;
+  float prev_scale;
+};
+// Host buffers the tap fills between the launches (every pointer may be null; include/s360_debug_flow_level.h)
+struct FlowLevelTaps {
+  float* gradients = nullptr;
+  float* initial_flow = nullptr;
+  float* blurred_flow = nullptr;
+  unsigned char* updated = nullptr;
+  unsigned* row_flags = nullptr;
+  float* sweep_forward = nullptr;
+  float* median_first = nullptr;
+  float* sweep_backward = nullptr;
+  float* median_second = nullptr;
+  float* diffused = nullptr;
+  float* final_flow = nullptr;
+};
+enum { kFlowLevelInfoCount = 8 };  // S360_FLI_*
+
 class FlowEngine {
  public:
   explicit FlowEngine(Profiler* prof) : prof_(prof), bufs_(std::make_shared<FlowBufs>()) {}
@@ -57,6 +92,11 @@ class FlowEngine {
   void share_buffers(const std::shared_ptr<FlowBufs>& b) { bufs_ = b; }
   const std::shared_ptr<FlowBufs>& buffers() const { return bufs_; }
   void compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatch& batch, int w, int h, int hint);
+  // test tap: one level on host planes (gray, alpha: N x h x w; init, prev: B x h x w x 2 or null; motion: N x h x w or null),
+  // in this engine's sweep mode; info: kFlowLevelInfoCount ints or null
+  void debug_level(hipStream_t st, const PixFlowConsts& pc, int N, int B, int w, int h, const float* gray, const float* alpha,
+                   const int* i0, const int* i1, const float* init, int hint, const float* prev, const float* motion,
+                   float prev_scale, const FlowLevelTaps& taps, int* info);
   // debugging taps for parity tests (valid after compute() + stream sync)
   const uchar4* dbg_down() const { return bufs_->down.as<uchar4>(); }
   const FlowLevels& levels() const { return lv_; }
@@ -75,6 +115,13 @@ class FlowEngine {
   TabSlot tabs_[4];
   int tab_next_ = 0;
   const unsigned long long* batch_tables(hipStream_t st, const FlowBatch& b);
+  // one pyramid level: gradients, (search init,) blur to records, sweep, median, sweep, median, diffusion (+ adjust); `tap`
+  // (tests only) copies the stage buffers to the host between the launches, with a stream sync each
+  void level(hipStream_t st, const PixFlowConsts& pc, const FlowLevelArgs& a, const FlowLevelTaps* tap = nullptr);
+  size_t handoff_bytes(int w, int h, int B) const;  // of one sweep launch, rounded up to 256
+  static size_t rowflag_bytes(int h, int B) { return ((size_t)B * h * sizeof(unsigned) + 255) & ~(size_t)255; }
+  bool sweeps_fast(hipStream_t st, const std::vector<float>& divisors);  // the fast division is on and verified for these
+  const BlurTaps tGrad_ = gaussian_taps(3, 0.5f), tFlow_ = gaussian_taps(15, 8.0f);
   std::shared_ptr<FlowBufs> bufs_;
   DevBuf err_;
   int sweep_mode_ = 2;      // 2: lockstep kernel (latency, default), 3: quad kernel (throughput)

@@ -75,6 +75,8 @@ void launch_resize_linear_f32(hipStream_t st, const float* src, int sw, int sh, 
 void launch_resize_cubic_f32c2(hipStream_t st, const float2* src, int sw, int sh, size_t sbs, float2* dst, int dw,
                                int dh, size_t dbs, int B, float post_scale, const float2* const* src_tab = nullptr);
 void launch_median5_c2(hipStream_t st, const float2* src, float2* dst, int w, int h, size_t bs, int B);
+// threads per tile row of the row-8 median that launch_median5_c2 gives a w x h level: 32 / 16 / 8 / 4, 0 = the narrow kernel
+int median5_tile_bx(int w, int h);
 // lockstep banded sweep (sweep_lock.hip): nw compute waves (4 rows each) + 2 service waves per workgroup
 int sweep_lock_waves();  // compute waves per workgroup: 2 (tools/sweep_microbench builds: S360_LOCK_NW = 1 / 2 / 4)
 int sweep_lock_num_wgs(int h, int nw);
@@ -88,6 +90,10 @@ void launch_sweep_lock(hipStream_t st, const float4* rec, const float2* G, float
 bool sweep_verify_divisors(hipStream_t st, const std::vector<float>& divisors);
 // throughput-oriented sweep (sweep_quad.hip): one wave per workgroup, 16 rows x 4 or 20 rows x 3 lanes per pixel, two rounds
 size_t sweep_quad_handoff_bytes(int w, int h, int B);
+// what a launch of B flows of h rows runs with: lanes per pixel (3 or 4), bands per flow, persistent waves (= workgroups)
+int sweep_quad_lanes_per_pixel(int h, int B);
+int sweep_quad_num_bands(int h, int B);
+int sweep_quad_waves(int h, int B);
 // rec: per flow and pixel the HALF-record {blurredFlow.x | NaN = not updated, blurredFlow.y} (launch_blur_to_records without G);
 // a pixel's record is completed with I0's gradient from plane idx.i0[b] of G
 void launch_sweep_quad(hipStream_t st, const float2* rec, const float2* G, float2* flow, void* handoff,

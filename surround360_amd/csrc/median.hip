@@ -224,15 +224,21 @@ static int median_forced_bx() {
   return v;
 }
 
+// threads per tile row of the row-8 kernel that takes a w x h level, 0 = the narrow kernel
+int median5_tile_bx(int w, int h) {
+  if (w < 64) return 0;  // 8 pixels per thread; narrow levels keep one pixel per thread (more threads than the chip otherwise idles)
+  int bx = median_forced_bx();
+  if (!bx) {
+    bx = 32;
+    for (int c : {16, 8, 4})
+      if (median_tile_cost(w, h, c) < median_tile_cost(w, h, bx)) bx = c;
+  }
+  return bx;
+}
+
 void launch_median5_c2(hipStream_t st, const float2* src, float2* dst, int w, int h, size_t bs, int B) {
   dim3 blk(64, 4);
-  if (w >= 64) {  // 8 pixels per thread; narrow levels keep one pixel per thread (more threads than the chip otherwise idles)
-    int bx = median_forced_bx();
-    if (!bx) {
-      bx = 32;
-      for (int c : {16, 8, 4})
-        if (median_tile_cost(w, h, c) < median_tile_cost(w, h, bx)) bx = c;
-    }
+  if (const int bx = median5_tile_bx(w, h)) {
     switch (bx) {
       case 32: launch_row8<32>(st, src, dst, w, h, bs, B); break;
       case 16: launch_row8<16>(st, src, dst, w, h, bs, B); break;

@@ -614,7 +614,24 @@ static int quad_lpp(int h, int B) {
   if (forced) return forced;
   return (long long)B * ((h + 15) / 16) >= 4096 ? 3 : 4;  // bands of 16 rows in the launch against 1024 SIMDs x 4
 }
+int sweep_quad_lanes_per_pixel(int h, int B) { return quad_lpp(h, B); }
 int sweep_quad_num_bands(int h, int B) { const int rows = quad_rows(quad_lpp(h, B)); return (h + rows - 1) / rows; }
+// Persistent waves of one launch: one per band and flow, capped at a few per CU (a wave that finishes a band takes the next ticket)
+int sweep_quad_waves(int h, int B) {
+  // S360_QUAD_WAVES_PER_CU: persistent waves per CU of one launch (tuning only; the results do not depend on it)
+  // (read at every launch: tools/overlap_probe.py changes it inside one process)
+  const int perCu = [] {
+    const char* e = std::getenv("S360_QUAD_WAVES_PER_CU");
+    const int v = e ? std::atoi(e) : 0;
+    return v > 0 ? v : 8;  // (two waves per SIMD)
+  }();
+  static const int cus = [] {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+  }();
+  return std::min(sweep_quad_num_bands(h, B) * B, cus * perCu);
+}
 size_t sweep_quad_handoff_bytes(int w, int h, int B) {
   return 256 + (size_t)B * sweep_quad_num_bands(h, B) * w * sizeof(unsigned long long);
 }
@@ -632,19 +649,7 @@ void launch_sweep_quad(hipStream_t st, const float2* rec, const float2* G, float
   // hand-off arena of all its sweep launches with one memset.
   unsigned* hdr = reinterpret_cast<unsigned*>(handoff);
   unsigned long long* H = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(handoff) + 256);
-  // S360_QUAD_WAVES_PER_CU: persistent waves per CU of one launch (tuning only; the results do not depend on it)
-  // (read at every launch: tools/overlap_probe.py changes it inside one process)
-  const int perCu = [] {
-    const char* e = std::getenv("S360_QUAD_WAVES_PER_CU");
-    const int v = e ? std::atoi(e) : 0;
-    return v > 0 ? v : 8;  // (two waves per SIMD)
-  }();
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  const int grid = std::min(nb * B, cus * perCu);
+  const int grid = sweep_quad_waves(h, B);
 #define S360_LAUNCH_QUAD(F, L)                                                                                       \
   hipLaunchKernelGGL((k_sweep_quad<F, L>), dim3(grid), dim3(64), 0, st, rec, G, flow, H, hdr, w, h, bs, idx, dir, c, \
                      fc, nb, B, errflag, rowflags)

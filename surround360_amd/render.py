@@ -190,6 +190,29 @@ class Context:
                                                _p(out), C.byref(tiled)))
         return out, bool(tiled.value)
 
+    def debug_flow_level(self, gray, alpha, i0, i1, initial_flow=None, alg="pixflow_low", hint="UNKNOWN", prev_flow=None, motion=None,
+                         prev_scale=1.0, want=None):
+        """One pyramid level of the flow engine (include/s360_debug_flow_level.h) on N grey and N alpha planes (N x h x w) for the
+        flows i0[b] -> i1[b], in the context's sweep mode. Returns ({stage: array}, {info name: int}); `want` names the stages
+        to hand out (default: all that exist for the call — no "diffused" with previous state)."""
+        gray, alpha = np.ascontiguousarray(gray, np.float32), np.ascontiguousarray(alpha, np.float32)
+        n, h, w = gray.shape
+        assert alpha.shape == gray.shape
+        i0, i1 = np.ascontiguousarray(i0, np.int32), np.ascontiguousarray(i1, np.int32)
+        b = len(i0)
+        f32 = lambda a, shape: None if a is None else np.ascontiguousarray(a, np.float32).reshape(shape)  # noqa: E731
+        init, prev, mo = f32(initial_flow, (b, h, w, 2)), f32(prev_flow, (b, h, w, 2)), f32(motion, (n, h, w))
+        shapes = {"gradients": ((n, h, w, 2), np.float32), "updated": ((b, h, w), np.uint8), "row_flags": ((b, h), np.uint32)}
+        names = [f[0] for f in _capi.FlowLevelOut._fields_]
+        if want is None:
+            want = [k for k in names if not (k == "diffused" and prev is not None)]
+        out = {k: np.empty(*shapes.get(k, ((b, h, w, 2), np.float32))) for k in want}
+        o = _capi.FlowLevelOut(**{k: _p(v) for k, v in out.items()})
+        info = np.zeros(_capi.FLOW_LEVEL_INFO_COUNT, np.int32)
+        self._ck(lib().s360_debug_flow_level(self.h, _p(gray), _p(alpha), n, w, h, _p(i0), _p(i1), b, _p(init), alg.encode(), HINT[hint],
+                                             _p(prev), _p(mo), C.c_float(prev_scale), C.byref(o), _p(info)))
+        return out, dict(zip(_capi.FLOW_LEVEL_INFO, (int(v) for v in info)))
+
     def spherical_warp_map(self, cam, dw, dh, l, r, t, b):
         m = np.empty((dh, dw, 2), np.float32)
         self._ck(lib().s360_spherical_warp_map(self.h, _p(m), dw, dh, C.byref(cam), C.c_float(l), C.c_float(r),

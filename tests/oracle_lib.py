@@ -309,6 +309,33 @@ def pixflow_level(I0, I1, a0, a1, flow=None, hint="UNKNOWN", search20=False):
     return f
 
 
+LEVEL_FLOW_STAGES = ("initial_flow", "blurred_flow", "sweep_forward", "median_first", "sweep_backward", "median_second", "diffused")
+
+
+def pixflow_level_stages(I0, I1, a0, a1, flow=None, hint="UNKNOWN", search20=False, prev_flow=None, motion=None, prev_scale=1.0):
+    """One level with its intermediates (oracle/pixflow.h: LevelStages): {"I0x", "I0y", "I1x", "I1y" (h x w), the flows of
+    LEVEL_FLOW_STAGES (h x w x 2), "updated" (h x w uint8), "final_flow"}. prev_flow + motion: adjustFlowTowardPrevious with the
+    previous flow multiplied by prev_scale first, as computeOpticalFlow applies it to a level; "final_flow" is then the adjusted
+    flow, the diffused one otherwise."""
+    h, w = I0.shape
+    assert (prev_flow is None) == (motion is None)
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)  # noqa: E731
+    out = {k: np.empty((h, w), np.float32) for k in ("I0x", "I0y", "I1x", "I1y")}
+    out.update({k: np.empty((h, w, 2), np.float32) for k in LEVEL_FLOW_STAGES})
+    out["updated"] = np.empty((h, w), np.uint8)
+    adjusted = np.empty((h, w, 2), np.float32) if prev_flow is not None else None
+    fn = lib().orc_pixflow_level_stages
+    fn.restype = None
+    fn.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 13
+    ins = [f32(I0), f32(I1), f32(a0), f32(a1), f32(flow), f32(prev_flow), f32(motion)]
+    fn(_p(ins[0]), _p(ins[1]), _p(ins[2]), _p(ins[3]), w, h, _p(ins[4]), HINT[hint], int(search20), _p(ins[5]), _p(ins[6]),
+       C.c_float(prev_scale), _p(out["I0x"]), _p(out["I0y"]), _p(out["I1x"]), _p(out["I1y"]), _p(out["initial_flow"]),
+       _p(out["blurred_flow"]), _p(out["updated"]), _p(out["sweep_forward"]), _p(out["median_first"]), _p(out["sweep_backward"]),
+       _p(out["median_second"]), _p(out["diffused"]), _p(adjusted))
+    out["final_flow"] = adjusted if adjusted is not None else out["diffused"]
+    return out
+
+
 # ---- geometry ---------------------------------------------------------------------
 def spherical_warp_map(cam, dw, dh, l, r, t, b):
     m = np.empty((dh, dw, 2), np.float32)
