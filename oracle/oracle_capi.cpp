@@ -98,6 +98,15 @@ void orc_remap_cubic_u8(const uint8_t* s, int sw, int sh, int c, const float* ma
   ImgU8 r = remapCubicU8(wrapU8(s, sw, sh, c), wrapF(map, dw, dh, 2));
   std::memcpy(d, r.d.data(), r.bytes());
 }
+// the 1024 x 16 integer weights of the 8-bit remap (initInterTab2D), as remapCubicU8 reads them
+void orc_bicubic_tab_i(short* out) { std::memcpy(out, bicubicTab().i, sizeof(bicubicTab().i)); }
+// poleToSideFlow's warp map of a flow (render.h: poleWarpMap)
+void orc_pole_warp_map(const float* flow, int extW, int rows, float poleCameraRadius, float phiRampStart, float phiMid, float* map) {
+  PoleRamp R;
+  R.poleCameraRadius = poleCameraRadius; R.phiRampStart = phiRampStart; R.phiMid = phiMid; R.phiRampEnd = phiMid;
+  ImgF r = poleWarpMap(wrapF(flow, extW, rows, 2), R);
+  std::memcpy(map, r.d.data(), r.bytes());
+}
 void orc_remap_cubic_f32(const float* s, int sw, int sh, int c, const float* map, int dw, int dh, float* d) {
   ImgF r = remapCubicF32(wrapF(s, sw, sh, c), wrapF(map, dw, dh, 2));
   std::memcpy(d, r.d.data(), r.bytes());

@@ -426,6 +426,21 @@ static inline PoleRamp poleRamp(const RigDescription& rig) {
   return r;
 }
 
+// TRSP:487-496: the warp of the extended fisheye image, the flow ramped in over the rows between phiRampStart and phiMid.
+static inline ImgF poleWarpMap(const ImgF& flow, const PoleRamp& R) {
+  const int extendedWidth = flow.w, rows = flow.h;
+  ImgF warp(extendedWidth, rows, 2);
+  for (int y = 0; y < rows; ++y) {
+    const float phi = R.poleCameraRadius * float(y + 0.5f) / float(rows);
+    const float alpha = 1.0f - rampf(phi, R.phiRampStart, R.phiMid);
+    for (int x = 0; x < extendedWidth; ++x) {
+      warp.at(y, x, 0) = float(x) + (1.0f - alpha) * flow.at(y, x, 0);
+      warp.at(y, x, 1) = float(y) + (1.0f - alpha) * flow.at(y, x, 1);
+    }
+  }
+  return warp;
+}
+
 struct PoleFlowState {  // what the reference persists for the next frame (TRSP:413-452)
   ImgU8 extendedSide, extendedFisheye;
   ImgF flow;
@@ -454,16 +469,7 @@ static inline ImgU8 poleToSideFlow(const RigDescription& rig, const RenderParams
   else pf.computeOpticalFlow(extSide, extFish, ImgF(), ImgU8(), ImgU8(), flow, HINT_DOWN);
 
   const PoleRamp R = poleRamp(rig);
-  ImgF warp(extendedWidth, rows, 2);
-  for (int y = 0; y < rows; ++y) {
-    const float phi = R.poleCameraRadius * float(y + 0.5f) / float(rows);
-    const float alpha = 1.0f - rampf(phi, R.phiRampStart, R.phiMid);
-    for (int x = 0; x < extendedWidth; ++x) {
-      warp.at(y, x, 0) = float(x) + (1.0f - alpha) * flow.at(y, x, 0);
-      warp.at(y, x, 1) = float(y) + (1.0f - alpha) * flow.at(y, x, 1);
-    }
-  }
-  ImgU8 warpedExt = remapCubicU8(extFish, warp);
+  ImgU8 warpedExt = remapCubicU8(extFish, poleWarpMap(flow, R));
   ImgU8 warped = cropCols(warpedExt, 0, cols);
   const int maxBlendX = int(float(cols) * (kExtendFrac - 1.0f));
   for (int y = 0; y < rows; ++y)

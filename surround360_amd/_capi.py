@@ -115,6 +115,8 @@ DEBUG_ISP_SYMBOLS = ["s360_debug_isp_stages"]
 DEBUG_FLOW_LEVEL_SYMBOLS = ["s360_debug_flow_level"]
 FLOW_LEVEL_INFO = ("lanes_per_pixel", "bands", "waves", "fast_division", "median_tile", "sweep_error")  # S360_FLI_*
 FLOW_LEVEL_INFO_COUNT = 8
+# ... and the ones include/s360_debug_remap.h declares
+DEBUG_REMAP_SYMBOLS = ["s360_debug_remap_packed", "s360_debug_pole_warp_packed", "s360_debug_remap_by_flow"]
 
 
 class FlowLevelOut(C.Structure):
@@ -198,6 +200,12 @@ def lib():
         L.s360_debug_flow_level.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(FlowLevelOut),
                                             C.c_void_p]
+        L.s360_debug_remap_packed.restype = C.c_int
+        L.s360_debug_remap_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3
+        L.s360_debug_pole_warp_packed.restype = C.c_int
+        L.s360_debug_pole_warp_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p] * 3
+        L.s360_debug_remap_by_flow.restype = C.c_int
+        L.s360_debug_remap_by_flow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.s360_isp_config_defaults.restype = None
         L.s360_isp_destroy.restype = None
         L.s360_isp_destroy.argtypes = [C.c_void_p]

@@ -13,6 +13,7 @@
 #include "../../include/s360_debug_final_flow.h"
 #include "../../include/s360_debug_flow_level.h"
 #include "../../include/s360_debug_isp.h"
+#include "../../include/s360_debug_remap.h"
 #include "ctx.hpp"
 #include "isp.hpp"
 #include "render.hpp"
@@ -548,6 +549,73 @@ int s360_debug_flow_level(s360_ctx* c, const float* gray, const float* alpha, in
     }
     c->flow->debug_level(c->st, pc, n_images, n_flows, w, h, gray, alpha, i0, i1, initial_flow, hint, prev_flow, motion, prev_scale, t,
                          info);
+  });
+}
+
+// test taps (include/s360_debug_remap.h): the frame's bicubic remap launchers on caller-made sources, maps and flows. Buffers of the
+// call's own; the outputs are uploaded first, so a word no workgroup stores comes back as the caller left it.
+int s360_debug_remap_packed(s360_ctx* c, const uint8_t* src, int sw, int sh, const float* map, int dw, int dh, int batch, int alpha_mode,
+                            int y_feather_start, int feather_size, int weights, uint8_t* dst, uint32_t* packed, int32_t* tiles) {
+  return guard(c, [&] {
+    need(c && src && map && dst && packed && tiles, "null argument");
+    need(sw > 0 && sh > 0 && dw > 0 && dh > 0 && batch >= 1 && batch <= 65535, "bad size");
+    need(alpha_mode >= 0 && alpha_mode <= 2 && weights >= 0 && weights <= 2, "bad mode");
+    need(alpha_mode == 0 || feather_size > 0, "the feather needs a positive size");
+    FrameState& F = frame_state(c);
+    need(weights != 2 || F.tab.dev.bicubic_res, "the host's rebuild of the weight table failed: no rebuilt weights");
+    const size_t B = batch, sn = (size_t)sw * sh, dn = (size_t)dw * dh, nt = remap_packed_tiles(dw, dh);
+    DevBuf dsrc, dmap, ddst, dpk, dtl;
+    dsrc.ensure(B * sn * 4); dmap.ensure(B * dn * sizeof(float2)); ddst.ensure(B * dn * 4); dpk.ensure(B * dn * 4); dtl.ensure(B * nt * 16);
+    h2d(c, dsrc.p, src, B * sn * 4);
+    h2d(c, dmap.p, map, B * dn * sizeof(float2));
+    h2d(c, ddst.p, dst, B * dn * 4);
+    h2d(c, dpk.p, packed, B * dn * 4);
+    h2d(c, dtl.p, tiles, B * nt * 16);
+    launch_remap_pack_map(c->st, dmap.as<float2>(), sw, sh, dw, dh, dpk.as<unsigned>(), dtl.p, batch);
+    launch_remap_cubic_u8c4_packed(c->st, dsrc.as<uchar4>(), sw, sh, dmap.as<float2>(), dpk.as<unsigned>(), dtl.p, ddst.as<uchar4>(), dw, dh,
+                                   F.tab.dev, alpha_mode, y_feather_start, feather_size, batch, weights);
+    d2h(c, dst, ddst.p, B * dn * 4);
+    d2h(c, packed, dpk.p, B * dn * 4);
+    d2h(c, tiles, dtl.p, B * nt * 16);
+  });
+}
+int s360_debug_pole_warp_packed(s360_ctx* c, const uint8_t* ext_fisheye, int ext_w, int rows, const float* flow, float pole_camera_radius,
+                                float phi_ramp_start, float phi_mid, float phi_ramp_end, uint8_t* warped, uint32_t* packed, int32_t* tiles) {
+  return guard(c, [&] {
+    need(c && ext_fisheye && flow && warped && packed && tiles, "null argument");
+    need(ext_w > 0 && rows > 0, "bad size");
+    FrameState& F = frame_state(c);
+    const size_t n = (size_t)ext_w * rows, nt = remap_packed_tiles(ext_w, rows);
+    PoleWarpParams pw{};
+    pw.cols = pw.extW = ext_w;
+    pw.rows = rows;
+    pw.poleCameraRadius = pole_camera_radius; pw.phiRampStart = phi_ramp_start; pw.phiMid = phi_mid; pw.phiRampEnd = phi_ramp_end;
+    DevBuf dsrc, dflow, ddst, dpk, dtl;
+    dsrc.ensure(n * 4); dflow.ensure(n * sizeof(float2)); ddst.ensure(n * 4); dpk.ensure(n * 4); dtl.ensure(nt * 16);
+    h2d(c, dsrc.p, ext_fisheye, n * 4);
+    h2d(c, dflow.p, flow, n * sizeof(float2));
+    h2d(c, ddst.p, warped, n * 4);
+    h2d(c, dpk.p, packed, n * 4);
+    h2d(c, dtl.p, tiles, nt * 16);
+    launch_pole_warp_packed(c->st, dsrc.as<uchar4>(), dflow.as<float2>(), ddst.as<uchar4>(), pw, F.tab.dev, dpk.as<unsigned>(), dtl.p);
+    d2h(c, warped, ddst.p, n * 4);
+    d2h(c, packed, dpk.p, n * 4);
+    d2h(c, tiles, dtl.p, nt * 16);
+  });
+}
+int s360_debug_remap_by_flow(s360_ctx* c, const uint8_t* src, int w, int h, const float* flow, uint8_t* dst) {
+  return guard(c, [&] {
+    need(c && src && flow && dst, "null argument");
+    need(w > 0 && h > 0, "bad size");
+    FrameState& F = frame_state(c);
+    const size_t n = (size_t)w * h;
+    DevBuf dsrc, dflow, ddst;
+    dsrc.ensure(n * 4); dflow.ensure(n * sizeof(float2)); ddst.ensure(n * 4);
+    h2d(c, dsrc.p, src, n * 4);
+    h2d(c, dflow.p, flow, n * sizeof(float2));
+    h2d(c, ddst.p, dst, n * 4);
+    launch_remap_by_flow(c->st, dsrc.as<uchar4>(), w, h, dflow.as<float2>(), ddst.as<uchar4>(), F.tab.dev);
+    d2h(c, dst, ddst.p, n * 4);
   });
 }
 

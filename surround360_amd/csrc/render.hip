@@ -94,7 +94,7 @@ void Tables::build(hipStream_t st, int std_feather) {
     if (pos >= 0) {
       const int k1 = pos >> 2, k2 = pos & 3;
       if (k1 < 2 || k2 < 2 || diff < -8192 || diff > 8191) rebuilt = false;
-      else res[e] = (short)((diff << 2) | ((k1 - 2) * 2 + (k2 - 2)));
+      else res[e] = (short)((diff * 4) | ((k1 - 2) * 2 + (k2 - 2)));  // (* 4, not << 2: the residue is negative as often as not)
     }
   }
   std::vector<float> t10(766), t5(766), fs(256);

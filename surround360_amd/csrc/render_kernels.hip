@@ -1920,7 +1920,7 @@ static bool remap_rebuild_weights() {
 }
 void launch_remap_cubic_u8c4_packed(hipStream_t st, const uchar4* src, int sw, int sh, const float2* map, const unsigned* packed,
                                     const void* tiles, uchar4* dst, int dw, int dh, const DevTables& T, int alpha_mode,
-                                    int yFeatherStart, int featherSize, int batch) {
+                                    int yFeatherStart, int featherSize, int batch, int weights) {
   MapFromBuffer mf{map, dw};
   const dim3 grid(cdiv(dw, PT_W), cdiv(dh, PT_H), batch), block(PT_W, PT_TY);
   const int4* t4 = reinterpret_cast<const int4*>(tiles);
@@ -1928,7 +1928,9 @@ void launch_remap_cubic_u8c4_packed(hipStream_t st, const uchar4* src, int sw, i
   const int nt = (int)remap_packed_tiles(dw, dh);
   // The weights are rebuilt in the kernel (WT) unless the host's rebuild of the table failed or S360_REMAP_REBUILD_WEIGHTS=0 asks
   // for the table (the A/B switch of round 6's measurement: the kernel's header)
-  const bool wt = remap_rebuild_weights() && T.bicubic_res;
+  // (weights 1 / 2: the test tap's choice, include/s360_debug_remap.h)
+  if (weights == 2 && !T.bicubic_res) throw std::runtime_error("packed remap: the rebuilt weights are not available");
+  const bool wt = weights == 1 ? false : weights == 2 ? true : (remap_rebuild_weights() && T.bicubic_res);
 #define S360_RP(A, W)                                                                                                              \
   hipLaunchKernelGGL((k_remap_cubic_u8c4_packed<MapFromBuffer, A, W>), grid, block, 0, st, src, sw, sh, packed, t4, mf, dst, dw, dh, \
                      T.bicubic_i, yFeatherStart, featherSize, sbs, dbs, nt, T.bicubic_w1, T.bicubic_res)

@@ -57,7 +57,8 @@ void launch_remap_pack_map(hipStream_t st, const float2* map, int sw, int sh, in
                            int batch = 1);
 void launch_remap_cubic_u8c4_packed(hipStream_t st, const uchar4* src, int sw, int sh, const float2* map, const unsigned* packed,
                                     const void* tiles, uchar4* dst, int dw, int dh, const DevTables& T, int alpha_mode,
-                                    int yFeatherStart, int featherSize, int batch = 1);
+                                    int yFeatherStart, int featherSize, int batch = 1,
+                                    int weights = 0 /* 0: as configured (S360_REMAP_REBUILD_WEIGHTS), 1: the table, 2: rebuilt in the kernel */);
 // overlap crops (TRSP:196-198) for pairs [p0,p1): out[j] = right part of proj p0+j, out[n+j] = left part of
 // proj (p0+j+1)%P, n = p1-p0
 void launch_crop_overlaps(hipStream_t st, const uchar4* proj, int camW, int camH, int P, int overlapW, uchar4* out,

@@ -213,6 +213,43 @@ class Context:
                                              _p(prev), _p(mo), C.c_float(prev_scale), C.byref(o), _p(info)))
         return out, dict(zip(_capi.FLOW_LEVEL_INFO, (int(v) for v in info)))
 
+    def debug_remap_packed(self, src, mp, alpha_mode=0, y_feather_start=0, feather_size=1, weights=0, fill=0):
+        """The frame's packed bicubic remap (include/s360_debug_remap.h) of B BGRA sources (B x sh x sw x 4) through B maps
+        (B x dh x dw x 2). Returns (images B x dh x dw x 4, packed dwords B x dh x dw, tile records B x ty x tx x 4); every byte of
+        the three is `fill` before the launches."""
+        src, mp = _u8(src), np.ascontiguousarray(mp, np.float32)
+        b, sh, sw = src.shape[:3]
+        dh, dw = mp.shape[1:3]
+        assert src.shape == (b, sh, sw, 4) and mp.shape == (b, dh, dw, 2)
+        dst = np.full((b, dh, dw, 4), fill, np.uint8)
+        packed = np.full((b, dh, dw), fill * 0x01010101, np.uint32)
+        tiles = np.full((b, -(-dh // 16), -(-dw // 64), 4), fill * 0x01010101, np.uint32).view(np.int32)
+        self._ck(lib().s360_debug_remap_packed(self.h, _p(src), sw, sh, _p(mp), dw, dh, b, alpha_mode, y_feather_start, feather_size,
+                                               weights, _p(dst), _p(packed), _p(tiles)))
+        return dst, packed, tiles
+
+    def debug_pole_warp_packed(self, ext_fisheye, flow, pole_camera_radius, phi_ramp_start, phi_mid, phi_ramp_end, fill=0):
+        """poleToSideFlow's ramped warp of an extended fisheye image (rows x extW x 4) by a flow (rows x extW x 2) through the
+        frame's launcher: (warped image, packed dwords, tile records), pre-filled as in debug_remap_packed."""
+        src, fl = _u8(ext_fisheye), np.ascontiguousarray(flow, np.float32)
+        rows, ext_w = src.shape[:2]
+        assert src.shape == (rows, ext_w, 4) and fl.shape == (rows, ext_w, 2)
+        dst = np.full((rows, ext_w, 4), fill, np.uint8)
+        packed = np.full((rows, ext_w), fill * 0x01010101, np.uint32)
+        tiles = np.full((-(-rows // 16), -(-ext_w // 64), 4), fill * 0x01010101, np.uint32).view(np.int32)
+        self._ck(lib().s360_debug_pole_warp_packed(self.h, _p(src), ext_w, rows, _p(fl), pole_camera_radius, phi_ramp_start, phi_mid,
+                                                   phi_ramp_end, _p(dst), _p(packed), _p(tiles)))
+        return dst, packed, tiles
+
+    def debug_remap_by_flow(self, src, flow, fill=0):
+        """Pole removal's warp: the BGRA image (h x w x 4) sampled at (x, y) + flow (h x w x 2); the output pre-filled with `fill`."""
+        src, fl = _u8(src), np.ascontiguousarray(flow, np.float32)
+        h, w = src.shape[:2]
+        assert src.shape == (h, w, 4) and fl.shape == (h, w, 2)
+        dst = np.full((h, w, 4), fill, np.uint8)
+        self._ck(lib().s360_debug_remap_by_flow(self.h, _p(src), w, h, _p(fl), _p(dst)))
+        return dst
+
     def spherical_warp_map(self, cam, dw, dh, l, r, t, b):
         m = np.empty((dh, dw, 2), np.float32)
         self._ck(lib().s360_spherical_warp_map(self.h, _p(m), dw, dh, C.byref(cam), C.c_float(l), C.c_float(r),

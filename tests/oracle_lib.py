@@ -144,6 +144,22 @@ def remap_cubic_u8(src, mp):
     return d
 
 
+def bicubic_tab_i():
+    """The 1024 x 16 integer weights remap_cubic_u8 uses (entry = (fraction index of y) * 32 + that of x; tap = row * 4 + column)."""
+    t = np.empty((1024, 16), np.int16)
+    lib().orc_bicubic_tab_i(_p(t))
+    return t
+
+
+def pole_warp_map(flow, pole_camera_radius, phi_ramp_start, phi_mid):
+    """poleToSideFlow's warp map of a flow (rows x extW x 2), by the oracle's own loop."""
+    f = np.ascontiguousarray(flow, np.float32)
+    rows, ext_w, _ = f.shape
+    m = np.empty_like(f)
+    lib().orc_pole_warp_map(_p(f), ext_w, rows, C.c_float(pole_camera_radius), C.c_float(phi_ramp_start), C.c_float(phi_mid), _p(m))
+    return m
+
+
 def remap_cubic_f32(src, mp):
     s = _f3(src)
     mp = np.ascontiguousarray(mp, np.float32)

@@ -302,7 +302,9 @@ def env(rig_small, oracle, s360lib):
 
 @pytest.mark.parametrize("src_kind,sc,dc", [("step", 3, 4), ("checker", 3, 3), ("checker", 4, 4)])
 def test_bicubic_remap_saturates(env, oracle, src_kind, sc, dc):
-    """bicubicRemapToSpherical of 0 / 255 sources: the bicubic overshoots below 0 and above 255 and sat_u8 clamps."""
+    """bicubicRemapToSpherical of 0 / 255 sources: the bicubic overshoots below 0 and above 255 and sat_u8 clamps — in
+    k_remap_cubic_u8c4_tiled, the kernel of this entry point; the same for the packed kernels of the frame's projections is
+    tests/test_gpu_remap_packed.py::test_checker_reaches_both_ends_of_the_saturation."""
     cam, ocam = env["side_cam"](0)
     src = K.grey(K.checker(CAM, CAM, 8)) if src_kind == "checker" else K.step_pair(CAM, CAM, 0, 255)[0][..., :3]
     if sc == 4:

@@ -56,7 +56,9 @@ def _noise(rng, h, w, c):
 
 @pytest.mark.parametrize("cam_idx,sc,dc,dw,dh", [(0, 3, 4, 219, 213), (5, 3, 3, 128, 97), (5, 4, 4, 65, 9)])
 def test_bicubic_remap_to_spherical(env, oracle, cam_idx, sc, dc, dw, dh):
-    """ImageWarper.cpp:143-197 for a side camera: odd destination sizes (partial 64x8 tiles), 3- and 4-channel."""
+    """ImageWarper.cpp:143-197 for a side camera: odd destination sizes (partial 64x8 tiles), 3- and 4-channel. The operator
+    entry point runs k_remap_cubic_u8c4_tiled, the kernel the frame keeps for pole removal; the frame's projections run the
+    packed pair (k_remap_pack + k_remap_cubic_u8c4_packed), which tests/test_gpu_remap_packed.py covers."""
     cam, ocam = env["side_cam"](cam_idx)
     src = env["side"][cam_idx]
     if sc == 4:
@@ -71,7 +73,8 @@ def test_bicubic_remap_to_spherical(env, oracle, cam_idx, sc, dc, dw, dh):
 
 def test_bicubic_remap_pole_camera(env, oracle):
     """The top fisheye into the polar cap (TRSP:662-668): the source box of a destination tile is large here, so both
-    the LDS-staged path and the gather fallback of the remap kernel are exercised."""
+    the LDS-staged path and the gather fallback of k_remap_cubic_u8c4_tiled are exercised (the kernel behind this entry point
+    and behind pole removal; the packed pair that renders the frame's projections: tests/test_gpu_remap_packed.py)."""
     cam, ocam = env["top_cam"]()
     got = env["ctx"].bicubic_remap_to_spherical(env["top"], cam, 300, 70, 4, 2 * np.pi, 0.0, np.pi / 2, np.pi / 2 - 0.6)
     want = oracle.bicubic_remap_to_spherical(ocam, env["top"], 300, 70, 4, 2 * np.pi, 0.0, np.pi / 2, np.pi / 2 - 0.6)
