@@ -173,6 +173,29 @@ int orc_pixflow_levels(int w, int h, int* lw /*cap 64*/, int* lh) {
   }
   return n;
 }
+// PixFlow::prepare of one pair: what computeOpticalFlow has in hand when its level loop starts. prev_flow and prev_i1: both or
+// neither (prevI0 is never read, PixFlow.h:106). A pyramid is handed out as its levels one after the other, finest first (P pixels,
+// the sizes are orc_pixflow_levels'); its level 0 is the pre-blurred grey / the alpha / the downscaled and scaled previous flow /
+// the motion map. Every output pointer may be null: down0, down1 (dh x dw x 4), pyr_I0, pyr_I1, pyr_A0, pyr_A1 (P floats each),
+// pyr_prev (P x 2, BEFORE the per-level scale), pyr_motion (P), factors (one per level). Returns the number of levels.
+int orc_pixflow_prepare(const uint8_t* i0, const uint8_t* i1, int w, int h, const float* prev_flow, const uint8_t* prev_i1, uint8_t* down0,
+                        uint8_t* down1, float* pyr_I0, float* pyr_I1, float* pyr_A0, float* pyr_A1, float* pyr_prev, float* pyr_motion,
+                        float* factors) {
+  PixFlow pf{PixFlowParams()};
+  PixFlow::Prepared R;
+  pf.prepare(wrapU8(i0, w, h, 4), wrapU8(i1, w, h, 4), prev_flow ? wrapF(prev_flow, w, h, 2) : ImgF(), ImgU8(),
+             prev_i1 ? wrapU8(prev_i1, w, h, 4) : ImgU8(), R);
+  if (down0) std::memcpy(down0, R.d0.d.data(), R.d0.bytes());
+  if (down1) std::memcpy(down1, R.d1.d.data(), R.d1.bytes());
+  auto put = [](float* dst, const std::vector<ImgF>& pyr) {
+    if (!dst) return;
+    for (const ImgF& i : pyr) { std::memcpy(dst, i.d.data(), i.bytes()); dst += i.d.size(); }
+  };
+  put(pyr_I0, R.pyrI0); put(pyr_I1, R.pyrI1); put(pyr_A0, R.pyrA0); put(pyr_A1, R.pyrA1);
+  put(pyr_prev, R.pyrPrev); put(pyr_motion, R.pyrMotion);
+  if (factors) for (size_t l = 0; l < R.prevScale.size(); ++l) factors[l] = R.prevScale[l];
+  return (int)R.pyrI0.size();
+}
 // OpticalFlowInterface::computeOpticalFlow (OpticalFlowInterface.h:34-41). prev_* nullable.
 // level_flows (nullable): concatenated per-level flow (coarsest first) for debugging.
 // Returns 0, or -1 for an unknown algorithm name (the reference throws VrCamException).

@@ -311,15 +311,29 @@ struct PixFlow {
       }
   }
 
-  // PixFlow.h:81-183. prevFlow/prevI0/prevI1 may be empty (first frame / photo).
-  void computeOpticalFlow(const ImgU8& rgba0, const ImgU8& rgba1, const ImgF& prevFlow, const ImgU8& prevI0,
-                          const ImgU8& prevI1, ImgF& flow, int hint) const {
+  // What computeOpticalFlow has in hand when its level loop starts (PixFlow.h:81-153), as prepare() leaves it
+  struct Prepared {
+    bool usePrev = false;
+    ImgU8 d0, d1;                                   // the downscaled images
+    ImgF I0, I1, alpha0, alpha1;                    // level 0: grey after the pre-blur, alpha
+    std::vector<ImgF> pyrI0, pyrI1, pyrA0, pyrA1;   // the four image pyramids
+    ImgF prevFlowDown, motion;                      // the previous flow downscaled and x rows_down / rows_full; the motion map
+    std::vector<ImgF> pyrPrev, pyrMotion;           // their pyramids; pyrPrev BEFORE the per-level scale ...
+    std::vector<float> prevScale;                   // ... which is this, per level (PixFlow.h:147-153)
+  };
+
+  // PixFlow.h:81-153: everything in front of the level loop. prevFlow/prevI0/prevI1 may be empty (first frame / photo).
+  void prepare(const ImgU8& rgba0, const ImgU8& rgba1, const ImgF& prevFlow, const ImgU8& prevI0, const ImgU8& prevI1,
+               Prepared& R) const {
     assert(rgba0.c == 4 && rgba1.c == 4);
-    const int ow = rgba0.w, oh = rgba0.h;
+    (void)prevI0;
     const int dw = int(rgba0.w * P.downscaleFactor), dh = int(rgba0.h * P.downscaleFactor);
-    ImgU8 d0 = resizeCubicU8(rgba0, dw, dh), d1 = resizeCubicU8(rgba1, dw, dh);
-    const bool usePrev = !prevFlow.empty();
-    ImgF prevFlowDown, motion;
+    R.d0 = resizeCubicU8(rgba0, dw, dh);
+    R.d1 = resizeCubicU8(rgba1, dw, dh);
+    const ImgU8 &d0 = R.d0, &d1 = R.d1;
+    const bool usePrev = R.usePrev = !prevFlow.empty();
+    ImgF& prevFlowDown = R.prevFlowDown;
+    ImgF& motion = R.motion;
     if (usePrev) {
       prevFlowDown = resizeCubicF32(prevFlow, dw, dh);
       const float s = float(prevFlowDown.h) / float(prevFlow.h);
@@ -349,18 +363,30 @@ struct PixFlow {
       }
     I0 = gaussianBlurF32(I0, kPreBlurKernelWidth, kPreBlurSigma);
     I1 = gaussianBlurF32(I1, kPreBlurKernelWidth, kPreBlurSigma);
-    if (dbg) { dbg->down0 = d0; dbg->down1 = d1; dbg->I0 = I0; dbg->I1 = I1; dbg->alpha0 = alpha0; dbg->alpha1 = alpha1; }
+    R.I0 = I0; R.I1 = I1; R.alpha0 = alpha0; R.alpha1 = alpha1;
 
-    std::vector<ImgF> pyrI0 = buildPyramid(I0), pyrI1 = buildPyramid(I1);
-    std::vector<ImgF> pyrA0 = buildPyramid(alpha0), pyrA1 = buildPyramid(alpha1);
-    std::vector<ImgF> pyrPrev, pyrMotion;
+    R.pyrI0 = buildPyramid(I0); R.pyrI1 = buildPyramid(I1);
+    R.pyrA0 = buildPyramid(alpha0); R.pyrA1 = buildPyramid(alpha1);
     if (usePrev) {
-      pyrPrev = buildPyramid(prevFlowDown);
-      pyrMotion = buildPyramid(motion);
-      for (size_t l = 0; l < pyrPrev.size(); ++l) {
-        const float s = float(pyrPrev[l].h) / float(pyrPrev[0].h);
-        for (float& v : pyrPrev[l].d) v *= s;
-      }
+      R.pyrPrev = buildPyramid(prevFlowDown);
+      R.pyrMotion = buildPyramid(motion);
+      for (size_t l = 0; l < R.pyrPrev.size(); ++l) R.prevScale.push_back(float(R.pyrPrev[l].h) / float(R.pyrPrev[0].h));
+    }
+  }
+
+  // PixFlow.h:81-183. prevFlow/prevI0/prevI1 may be empty (first frame / photo).
+  void computeOpticalFlow(const ImgU8& rgba0, const ImgU8& rgba1, const ImgF& prevFlow, const ImgU8& prevI0,
+                          const ImgU8& prevI1, ImgF& flow, int hint) const {
+    const int ow = rgba0.w, oh = rgba0.h;
+    Prepared R;
+    prepare(rgba0, rgba1, prevFlow, prevI0, prevI1, R);
+    const bool usePrev = R.usePrev;
+    if (dbg) { dbg->down0 = R.d0; dbg->down1 = R.d1; dbg->I0 = R.I0; dbg->I1 = R.I1; dbg->alpha0 = R.alpha0; dbg->alpha1 = R.alpha1; }
+    const std::vector<ImgF>&pyrI0 = R.pyrI0, &pyrI1 = R.pyrI1, &pyrA0 = R.pyrA0, &pyrA1 = R.pyrA1, &pyrMotion = R.pyrMotion;
+    std::vector<ImgF>& pyrPrev = R.pyrPrev;
+    for (size_t l = 0; l < pyrPrev.size(); ++l) {
+      const float s = R.prevScale[l];
+      for (float& v : pyrPrev[l].d) v *= s;
     }
     flow = ImgF();
     const float invPyr = 1.0f / P.pyrScaleFactor;

@@ -117,6 +117,14 @@ FLOW_LEVEL_INFO = ("lanes_per_pixel", "bands", "waves", "fast_division", "median
 FLOW_LEVEL_INFO_COUNT = 8
 # ... and the ones include/s360_debug_remap.h declares
 DEBUG_REMAP_SYMBOLS = ["s360_debug_remap_packed", "s360_debug_pole_warp_packed", "s360_debug_remap_by_flow"]
+# ... and the ones include/s360_debug_flow_pyramid.h declares
+DEBUG_FLOW_PYRAMID_SYMBOLS = ["s360_debug_flow_prepare", "s360_debug_resize_linear_f32", "s360_debug_resize_cubic_flow"]
+
+
+class FlowPrepareOut(C.Structure):
+    """s360_flow_prepare_out (include/s360_debug_flow_pyramid.h)."""
+    _fields_ = [("cap_levels", C.c_int), ("cap_pixels", C.c_size_t)] + \
+               [(n, C.c_void_p) for n in ("level_w", "level_h", "n_levels", "factors", "pyr_images", "prev_pyr", "motion_pyr")]
 
 
 class FlowLevelOut(C.Structure):
@@ -200,6 +208,13 @@ def lib():
         L.s360_debug_flow_level.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.POINTER(FlowLevelOut),
                                             C.c_void_p]
+        L.s360_debug_flow_prepare.restype = C.c_int
+        L.s360_debug_flow_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_char_p, C.c_int, C.POINTER(FlowPrepareOut)]
+        L.s360_debug_resize_linear_f32.restype = C.c_int
+        L.s360_debug_resize_linear_f32.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]
+        L.s360_debug_resize_cubic_flow.restype = C.c_int
+        L.s360_debug_resize_cubic_flow.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p]
         L.s360_debug_remap_packed.restype = C.c_int
         L.s360_debug_remap_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3
         L.s360_debug_pole_warp_packed.restype = C.c_int

@@ -12,6 +12,7 @@
 #include "../../include/s360_debug.h"
 #include "../../include/s360_debug_final_flow.h"
 #include "../../include/s360_debug_flow_level.h"
+#include "../../include/s360_debug_flow_pyramid.h"
 #include "../../include/s360_debug_isp.h"
 #include "../../include/s360_debug_remap.h"
 #include "ctx.hpp"
@@ -549,6 +550,91 @@ int s360_debug_flow_level(s360_ctx* c, const float* gray, const float* alpha, in
     }
     c->flow->debug_level(c->st, pc, n_images, n_flows, w, h, gray, alpha, i0, i1, initial_flow, hint, prev_flow, motion, prev_scale, t,
                          info);
+  });
+}
+
+// test taps (include/s360_debug_flow_pyramid.h): the flow engine's preparation on caller-made images, and the pyramids' two resizes on
+// caller-made planes. Buffers of the call's own; a resize's output is uploaded first, so a word no thread stores comes back as the
+// caller left it.
+int s360_debug_flow_prepare(s360_ctx* c, const uint8_t* images, int n_images, int w, int h, const int* i0, const int* i1, int n_flows,
+                            const uint8_t* prev_images, const float* prev_flows, const char* alg, int fill,
+                            const s360_flow_prepare_out* out) {
+  return guard(c, [&] {
+    need(c && images && i0 && i1 && alg && out, "null argument");
+    need(w > 0 && h > 0 && n_images >= 1 && n_images <= kMaxFlows && n_flows >= 1 && n_flows <= kMaxFlows, "bad size");
+    need((prev_images != nullptr) == (prev_flows != nullptr), "previous images and previous flows must be given together");
+    need(fill >= -1 && fill <= 255, "bad fill byte");
+    const PixFlowConsts pc = pixflow_consts_by_name(alg);
+    const size_t n = (size_t)w * h, N = n_images, B = n_flows;
+    DevBuf dimg;
+    dimg.ensure(N * n * 4);
+    h2d(c, dimg.p, images, N * n * 4);
+    std::vector<DevBuf> pimg(prev_images ? N : 0), pflow(prev_flows ? B : 0);  // one allocation each, as a frame's state arrives
+    FlowBatch fb;
+    fb.add_images(dimg.as<uchar4>(), n_images, n);
+    for (size_t k = 0; k < pimg.size(); ++k) {
+      pimg[k].ensure(n * 4);
+      h2d(c, pimg[k].p, prev_images + k * n * 4, n * 4);
+      fb.prev_images.push_back(pimg[k].as<uchar4>());
+    }
+    for (size_t b = 0; b < B; ++b) {
+      if (prev_flows) {
+        pflow[b].ensure(n * sizeof(float2));
+        h2d(c, pflow[b].p, prev_flows + b * n * 2, n * sizeof(float2));
+      }
+      fb.add_flow(i0[b], i1[b], nullptr, prev_flows ? pflow[b].as<float2>() : nullptr);
+    }
+    FlowPrepareTaps t;
+    t.cap_levels = out->cap_levels; t.cap_pixels = out->cap_pixels;
+    t.level_w = out->level_w; t.level_h = out->level_h; t.n_levels = out->n_levels; t.factors = out->factors;
+    t.pyr_images = out->pyr_images; t.prev_pyr = out->prev_pyr; t.motion_pyr = out->motion_pyr;
+    c->flow->debug_prepare(c->st, pc, fb, w, h, fill, t);
+  });
+}
+int s360_debug_resize_linear_f32(s360_ctx* c, const float* src, int sw, int sh, int cn, int planes, int dw, int dh, float post_scale,
+                                 int do_scale, float* dst, int* tiled) {
+  return guard(c, [&] {
+    need(!dst || (c && src), "null argument");
+    need(sw > 0 && sh > 0 && dw > 0 && dh > 0 && planes >= 1 && planes <= kMaxFlows && (cn == 1 || cn == 2), "bad size");
+    if (tiled) *tiled = resize_linear_f32_tiled(sw, sh, dw, dh, cn) ? 1 : 0;
+    if (!dst) return;
+    const size_t ns = (size_t)sw * sh, nd = (size_t)dw * dh, B = planes;
+    DevBuf dsrc, ddst;
+    dsrc.ensure(B * ns * cn * sizeof(float)); ddst.ensure(B * nd * cn * sizeof(float));
+    h2d(c, dsrc.p, src, B * ns * cn * sizeof(float));
+    h2d(c, ddst.p, dst, B * nd * cn * sizeof(float));
+    launch_resize_linear_f32(c->st, dsrc.as<float>(), sw, sh, ns, ddst.as<float>(), dw, dh, nd, cn, planes, post_scale, do_scale);
+    d2h(c, dst, ddst.p, B * nd * cn * sizeof(float));
+  });
+}
+int s360_debug_resize_cubic_flow(s360_ctx* c, const float* src, int sw, int sh, int n_flows, int dw, int dh, float post_scale,
+                                 int through_table, float* dst, int* tiled) {
+  return guard(c, [&] {
+    need(!dst || (c && src), "null argument");
+    need(sw > 0 && sh > 0 && dw > 0 && dh > 0 && n_flows >= 1 && n_flows <= kMaxFlows, "bad size");
+    if (tiled) *tiled = resize_cubic_f32c2_tiled(sw, sh, dw, dh, through_table != 0) ? 1 : 0;
+    if (!dst) return;
+    const size_t ns = (size_t)sw * sh, nd = (size_t)dw * dh, B = n_flows;
+    DevBuf dsrc, ddst, dtab;
+    std::vector<DevBuf> srcs(through_table ? B : 0);
+    std::vector<const float2*> tab(B);  // (lives until the download below has synchronised the stream)
+    ddst.ensure(B * nd * sizeof(float2));
+    h2d(c, ddst.p, dst, B * nd * sizeof(float2));
+    if (through_table) {
+      for (size_t b = 0; b < B; ++b) {
+        srcs[b].ensure(ns * sizeof(float2));
+        h2d(c, srcs[b].p, src + b * ns * 2, ns * sizeof(float2));
+        tab[b] = srcs[b].as<float2>();
+      }
+      dtab.ensure(B * sizeof(void*));
+      h2d(c, dtab.p, tab.data(), B * sizeof(void*));
+      launch_resize_cubic_f32c2(c->st, nullptr, sw, sh, 0, ddst.as<float2>(), dw, dh, nd, n_flows, post_scale, dtab.as<const float2*>());
+    } else {
+      dsrc.ensure(B * ns * sizeof(float2));
+      h2d(c, dsrc.p, src, B * ns * sizeof(float2));
+      launch_resize_cubic_f32c2(c->st, dsrc.as<float2>(), sw, sh, ns, ddst.as<float2>(), dw, dh, nd, n_flows, post_scale);
+    }
+    d2h(c, dst, ddst.p, B * nd * sizeof(float2));
   });
 }
 

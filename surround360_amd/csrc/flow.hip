@@ -90,7 +90,7 @@ const unsigned long long* FlowEngine::batch_tables(hipStream_t st, const FlowBat
   return t.buf.as<unsigned long long>() + 2;
 }
 
-void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatch& batch, int w, int h, int hint) {
+FlowPrepared FlowEngine::prepare(hipStream_t st, const PixFlowConsts& pc, const FlowBatch& batch, int w, int h) {
   const int N = (int)batch.images.size(), B = (int)batch.out.size();
   if (B < 1 || B > kMaxFlows || (int)batch.i0.size() != B || (int)batch.i1.size() != B)
     throw Error(-1, "FlowEngine: bad batch");
@@ -114,10 +114,12 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
   const uchar4* const* imageTab = reinterpret_cast<const uchar4* const*>(tab);
   const uchar4* const* prevImageTab = reinterpret_cast<const uchar4* const*>(tab + N);
   const float2* const* prevFlowTab = reinterpret_cast<const float2* const*>(tab + 2 * N);
-  float* const* outTab = reinterpret_cast<float* const*>(tab + 2 * N + B);
-  FlowIdx idx;
-  idx.i0 = reinterpret_cast<const int*>(tab + 2 * N + 2 * B);
-  idx.i1 = idx.i0 + B;
+  FlowPrepared p;
+  p.N = N; p.B = B; p.L = L;
+  p.usePrev = usePrev;
+  p.outTab = reinterpret_cast<float* const*>(tab + 2 * N + B);
+  p.idx.i0 = reinterpret_cast<const int*>(tab + 2 * N + 2 * B);
+  p.idx.i1 = p.idx.i0 + B;
 
   M.down.ensure(N * n0 * sizeof(uchar4));
   M.gray.ensure(N * n0 * sizeof(float));
@@ -131,24 +133,24 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
     divs.push_back((float)lv_.w[l]);
     divs.push_back((float)lv_.h[l]);
   }
-  const bool fastOk = sweeps_fast(st, divs);
+  p.fast = sweeps_fast(st, divs);
   M.rec.ensure(B * n0 * (sweep_mode_ == 3 ? sizeof(float2) : sizeof(float4)));  // half-records / full records (flow_kernels.hpp)
   // Band hand-off granules + ticket counters of every sweep launch of this call (2 per level): one arena, reset to
   // all-ones ("not written") by ONE memset instead of one per launch.
   // + per level one word per (flow, row): all-ones = no pixel of the row is updated (written by the record kernel)
-  std::vector<size_t> hoff(L + 1, 0);
-  for (int l = 0; l < L; ++l) hoff[l + 1] = hoff[l] + 2 * handoff_bytes(lv_.w[l], lv_.h[l], B) + rowflag_bytes(lv_.h[l], B);
-  M.handoff.ensure(hoff[L]);
-  S360_HIP(hipMemsetAsync(M.handoff.p, 0xFF, hoff[L], st));
+  p.hoff.assign(L + 1, 0);
+  for (int l = 0; l < L; ++l) p.hoff[l + 1] = p.hoff[l] + 2 * handoff_bytes(lv_.w[l], lv_.h[l], B) + rowflag_bytes(lv_.h[l], B);
+  M.handoff.ensure(p.hoff[L]);
+  S360_HIP(hipMemsetAsync(M.handoff.p, 0xFF, p.hoff[L], st));
   if (!err_.p) {
     err_.ensure(sizeof(unsigned));
     S360_HIP(hipMemsetAsync(err_.p, 0, sizeof(unsigned), st));
   }
-  float* pyrI = M.pyrI.as<float>();
-  auto LI = [&](int l) { return pyrI + (size_t)2 * N * lv_.off[l]; };
-  auto LA = [&](int l) { return pyrI + (size_t)2 * N * lv_.off[l] + (size_t)N * lv_.w[l] * lv_.h[l]; };
+  p.pyrI = M.pyrI.as<float>();
+  auto LI = [&](int l) { return level_gray(p, l); };
+  auto LA = [&](int l) { return level_alpha(p, l); };
 
-  const BlurTaps tPre = gaussian_taps(5, 0.25f), tFinal = gaussian_taps(3, 1.0f);
+  const BlurTaps tPre = gaussian_taps(5, 0.25f);
   {
     ProfScope ps(P, "flow_entry");
     // the downscaled image itself is read again only by k_motion (temporal state): stored only then
@@ -165,15 +167,13 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
                                0);
     }
   }
-  float2* prevPyr = nullptr;
-  float* motionPyr = nullptr;
   if (usePrev) {
     ProfScope ps(P, "flow_prev");
     M.prevdown.ensure(N * n0 * sizeof(uchar4));
     M.prevPyr.ensure(B * lv_.total * sizeof(float2));
     M.motionPyr.ensure(N * lv_.total * sizeof(float));
-    prevPyr = M.prevPyr.as<float2>();
-    motionPyr = M.motionPyr.as<float>();
+    float2* prevPyr = p.prevPyr = M.prevPyr.as<float2>();
+    float* motionPyr = p.motionPyr = M.motionPyr.as<float>();
     launch_resize_cubic_u8c4(st, nullptr, w, h, 0, M.prevdown.as<uchar4>(), dw_, dh_, n0, N, prevImageTab);
     launch_motion(st, M.down.as<uchar4>(), M.prevdown.as<uchar4>(), n0, n0, motionPyr, n0, N);
     // prevFlowDownscaled = resize(prevFlow) * (rows_down / rows_full)  (PixFlow.h:103-104)
@@ -186,9 +186,17 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
                                motionPyr + (size_t)N * lv_.off[l], lv_.w[l], lv_.h[l], nd, 1, N, 1.f, 0);
     }
     // (the rescale of the previous flow at each level, PixFlow.h:147-153 — level 0's factor is exactly 1 —, is applied where the
-    // level is read: launch_diffusion_adjust below)
+    // level is read: launch_diffusion_adjust)
   }
+  return p;
+}
 
+void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatch& batch, int w, int h, int hint) {
+  const FlowPrepared p = prepare(st, pc, batch, w, h);
+  const int N = p.N, B = p.B, L = p.L;
+  Profiler& P = *prof_;
+  FlowBufs& M = *bufs_;
+  const BlurTaps tFinal = gaussian_taps(3, 1.0f);
   float2* cur = M.flowA.as<float2>();
   float2* oth = M.flowB.as<float2>();
   const float invPyr = 1.0f / pc.pyrScaleFactor;
@@ -199,18 +207,18 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
     // (the rescale of the previous flow's level, PixFlow.h:147-153, is applied where it is read; level 0's factor is exactly 1)
     FlowLevelArgs a;
     a.w = wl; a.h = hl; a.N = N; a.B = B;
-    a.I = LI(l); a.A = LA(l);
-    a.idx = idx;
+    a.I = level_gray(p, l); a.A = level_alpha(p, l);
+    a.idx = p.idx;
     a.cur = cur; a.oth = oth;
     a.first = l == L - 1;
     a.hint = hint;
-    a.handoff_fwd = (char*)M.handoff.p + hoff[l];
-    a.handoff_bwd = (char*)M.handoff.p + hoff[l] + handoff_bytes(wl, hl, B);
-    a.rowflags = reinterpret_cast<unsigned*>((char*)M.handoff.p + hoff[l] + 2 * handoff_bytes(wl, hl, B));
-    a.fast = fastOk;
-    a.prev = usePrev ? prevPyr + (size_t)B * lv_.off[l] : nullptr;
-    a.motion = usePrev ? motionPyr + (size_t)N * lv_.off[l] : nullptr;
-    a.prev_scale = l == 0 ? 1.0f : float(lv_.h[l]) / float(lv_.h[0]);
+    a.handoff_fwd = (char*)M.handoff.p + p.hoff[l];
+    a.handoff_bwd = (char*)M.handoff.p + p.hoff[l] + handoff_bytes(wl, hl, B);
+    a.rowflags = reinterpret_cast<unsigned*>((char*)M.handoff.p + p.hoff[l] + 2 * handoff_bytes(wl, hl, B));
+    a.fast = p.fast;
+    a.prev = p.usePrev ? p.prevPyr + (size_t)B * lv_.off[l] : nullptr;
+    a.motion = p.usePrev ? p.motionPyr + (size_t)N * lv_.off[l] : nullptr;
+    a.prev_scale = level_prev_scale(l);
     level(st, pc, a);
     if (capture_levels) {
       std::vector<float> hbuf(B * nl * 2);
@@ -225,8 +233,45 @@ void FlowEngine::compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatc
     } else {
       ProfScope ps(P, "flow_final");
       // final upscale + scalar + 3x3 blur fused: the upscaled flow is evaluated while the blur's tile is loaded
-      launch_upscale_blur(st, oth, wl, hl, nl, nullptr, w, h, (size_t)w * h, B, 1.0f / pc.downscaleFactor, tFinal, outTab);
+      launch_upscale_blur(st, oth, wl, hl, nl, nullptr, w, h, (size_t)w * h, B, 1.0f / pc.downscaleFactor, tFinal, p.outTab);
     }
+  }
+}
+
+void FlowEngine::debug_prepare(hipStream_t st, const PixFlowConsts& pc, const FlowBatch& batch, int w, int h, int fill,
+                               const FlowPrepareTaps& t) {
+  FlowBufs& M = *bufs_;
+  const int N = (int)batch.images.size(), B = (int)batch.out.size();
+  const int dw = int(w * pc.downscaleFactor), dh = int(h * pc.downscaleFactor);
+  if (fill >= 0 && dw >= 2 && dh >= 2 && N >= 1 && B >= 1) {  // every buffer the preparation writes holds `fill` before it runs
+    FlowLevels lv;
+    lv.build(dw, dh, pc.pyrScaleFactor);
+    const size_t n0 = (size_t)dw * dh;
+    const bool usePrev = !batch.prev_flow.empty();
+    struct { DevBuf* b; size_t bytes; } bufs[] = {{&M.down, N * n0 * sizeof(uchar4)}, {&M.gray, N * n0 * sizeof(float)},
+                                                  {&M.pyrI, 2 * N * lv.total * sizeof(float)}, {&M.prevdown, N * n0 * sizeof(uchar4)},
+                                                  {&M.prevPyr, B * lv.total * sizeof(float2)}, {&M.motionPyr, N * lv.total * sizeof(float)}};
+    for (int k = 0; k < (usePrev ? 6 : 3); ++k) {
+      bufs[k].b->ensure(bufs[k].bytes);
+      S360_HIP(hipMemsetAsync(bufs[k].b->p, fill, bufs[k].b->cap, st));
+    }
+  }
+  const FlowPrepared p = prepare(st, pc, batch, w, h);
+  S360_HIP(hipStreamSynchronize(st));
+  if (p.L > t.cap_levels || lv_.total > t.cap_pixels) throw Error(-1, "FlowEngine: the tap's buffers are too small for this pyramid");
+  auto grab = [&](void* host, const void* dev, size_t bytes) {
+    if (host) S360_HIP(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost));
+  };
+  for (int l = 0; l < p.L; ++l) {
+    if (t.level_w) t.level_w[l] = lv_.w[l];
+    if (t.level_h) t.level_h[l] = lv_.h[l];
+    if (t.factors) t.factors[l] = level_prev_scale(l);
+  }
+  if (t.n_levels) *t.n_levels = p.L;
+  grab(t.pyr_images, p.pyrI, 2 * (size_t)N * lv_.total * sizeof(float));
+  if (p.usePrev) {
+    grab(t.prev_pyr, p.prevPyr, (size_t)B * lv_.total * sizeof(float2));
+    grab(t.motion_pyr, p.motionPyr, (size_t)N * lv_.total * sizeof(float));
   }
 }
 

@@ -85,6 +85,32 @@ struct FlowLevelTaps {
 };
 enum { kFlowLevelInfoCount = 8 };  // S360_FLI_*
 
+// What compute()'s preparation (FlowEngine::prepare) leaves for the level loop: the batch's tables, the image pyramids, and with
+// previous state the previous flow's and the motion's pyramids, all in the engine's buffers
+struct FlowPrepared {
+  int N = 0, B = 0, L = 0;
+  bool usePrev = false;
+  bool fast = false;             // the sweeps' verified fast division
+  FlowIdx idx{nullptr, nullptr};
+  float* const* outTab = nullptr;
+  float* pyrI = nullptr;         // per level: N grey planes, then N alpha planes
+  float2* prevPyr = nullptr;     // per level: B planes, before the level's rescale (level_prev_scale)
+  float* motionPyr = nullptr;    // per level: N planes
+  std::vector<size_t> hoff;      // per level: offset of its hand-off arenas and row flags
+};
+// Host buffers the preparation's tap fills (every pointer may be null; include/s360_debug_flow_pyramid.h)
+struct FlowPrepareTaps {
+  int cap_levels = 0;            // entries of level_w / level_h / factors
+  size_t cap_pixels = 0;         // pixels of one plane's pyramid that the three arrays below have room for
+  int* level_w = nullptr;
+  int* level_h = nullptr;
+  int* n_levels = nullptr;
+  float* factors = nullptr;
+  float* pyr_images = nullptr;   // the engine's layout, see FlowPrepared
+  float* prev_pyr = nullptr;
+  float* motion_pyr = nullptr;
+};
+
 class FlowEngine {
  public:
   explicit FlowEngine(Profiler* prof) : prof_(prof), bufs_(std::make_shared<FlowBufs>()) {}
@@ -92,6 +118,8 @@ class FlowEngine {
   void share_buffers(const std::shared_ptr<FlowBufs>& b) { bufs_ = b; }
   const std::shared_ptr<FlowBufs>& buffers() const { return bufs_; }
   void compute(hipStream_t st, const PixFlowConsts& pc, const FlowBatch& batch, int w, int h, int hint);
+  // test tap: the preparation alone on a batch of device images; fill >= 0: every buffer it writes holds that byte before
+  void debug_prepare(hipStream_t st, const PixFlowConsts& pc, const FlowBatch& batch, int w, int h, int fill, const FlowPrepareTaps& t);
   // test tap: one level on host planes (gray, alpha: N x h x w; init, prev: B x h x w x 2 or null; motion: N x h x w or null),
   // in this engine's sweep mode; info: kFlowLevelInfoCount ints or null
   void debug_level(hipStream_t st, const PixFlowConsts& pc, int N, int B, int w, int h, const float* gray, const float* alpha,
@@ -115,6 +143,13 @@ class FlowEngine {
   TabSlot tabs_[4];
   int tab_next_ = 0;
   const unsigned long long* batch_tables(hipStream_t st, const FlowBatch& b);
+  // everything in front of compute()'s level loop: checks, tables, buffers, entry downscale, pre-blur, image pyramid, and with
+  // previous state the previous images, the motion, the previous flow and their pyramids
+  FlowPrepared prepare(hipStream_t st, const PixFlowConsts& pc, const FlowBatch& batch, int w, int h);
+  float* level_gray(const FlowPrepared& p, int l) const { return p.pyrI + (size_t)2 * p.N * lv_.off[l]; }
+  float* level_alpha(const FlowPrepared& p, int l) const { return level_gray(p, l) + (size_t)p.N * lv_.w[l] * lv_.h[l]; }
+  // what a level multiplies the previous flow by as it reads it (PixFlow.h:147-153)
+  float level_prev_scale(int l) const { return l == 0 ? 1.0f : float(lv_.h[l]) / float(lv_.h[0]); }
   // one pyramid level: gradients, (search init,) blur to records, sweep, median, sweep, median, diffusion (+ adjust); `tap`
   // (tests only) copies the stage buffers to the host between the launches, with a stream sync each
   void level(hipStream_t st, const PixFlowConsts& pc, const FlowLevelArgs& a, const FlowLevelTaps* tap = nullptr);

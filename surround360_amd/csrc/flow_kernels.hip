@@ -1416,16 +1416,20 @@ void launch_blur_to_records(hipStream_t st, const float2* flow, void* rec, int w
   if (G) launch_sepblur_t<7, 2, 3, 0>(st, (const float*)flow, nullptr, w, h, bs, B, t, A, idx, G, rec, nullptr, UpSrc{}, rowflags);
   else launch_sepblur_t<7, 2, 2, 0>(st, (const float*)flow, nullptr, w, h, bs, B, t, A, idx, nullptr, rec, nullptr, UpSrc{}, rowflags);
 }
-void launch_resize_linear_f32(hipStream_t st, const float* src, int sw, int sh, size_t sbs, float* dst, int dw, int dh,
-                              size_t dbs, int cn, int B, float post_scale, int do_scale) {
+bool resize_linear_f32_tiled(int sw, int sh, int dw, int dh, int cn) {
   const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
-  const int ppt = (B % 4 == 0) ? 4 : (B % 2 == 0) ? 2 : 1;  // planes per thread (the coordinates are computed once)
   // one-channel planes (the image pyramids): tiled, if a tile's source box fits — x0.9 levels do, the smallest levels'
   // rounded sizes may not
   const int tw = std::min(dw, RL_TW), th = std::min(dh, RL_TH);
   const bool fits = std::min(sw, (int)std::floor((tw - 1) * scx) + 3) + 3 <= RL_BW &&
                     std::min(sh, (int)std::floor((th - 1) * scy) + 3) <= RL_BH;
-  if (cn == 1 && fits) {
+  return cn == 1 && fits;
+}
+void launch_resize_linear_f32(hipStream_t st, const float* src, int sw, int sh, size_t sbs, float* dst, int dw, int dh,
+                              size_t dbs, int cn, int B, float post_scale, int do_scale) {
+  const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
+  const int ppt = (B % 4 == 0) ? 4 : (B % 2 == 0) ? 2 : 1;  // planes per thread (the coordinates are computed once)
+  if (resize_linear_f32_tiled(sw, sh, dw, dh, cn)) {
     const dim3 grid((dw + RL_TW - 1) / RL_TW, (dh + RL_TH - 1) / RL_TH, B / ppt);
 #define S360_RLT(P)                                                                                                   \
   hipLaunchKernelGGL((k_resize_linear_f32c1_tiled<P>), grid, dim3(256), 0, st, src, sw, sh, sbs, dst, dw, dh, dbs, scx, \
@@ -1442,10 +1446,14 @@ void launch_resize_linear_f32(hipStream_t st, const float* src, int sw, int sh, 
   else { if (ppt == 4) S360_RL(2, 4); else if (ppt == 2) S360_RL(2, 2); else S360_RL(2, 1); }
 #undef S360_RL
 }
+bool resize_cubic_f32c2_tiled(int sw, int sh, int dw, int dh, bool src_tab) {
+  const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
+  return !src_tab && scx <= 1.0 && scy <= 1.0;  // upscale: a 64x16 tile reads at most (64 + 4) x (16 + 4) source pixels
+}
 void launch_resize_cubic_f32c2(hipStream_t st, const float2* src, int sw, int sh, size_t sbs, float2* dst, int dw,
                                int dh, size_t dbs, int B, float post_scale, const float2* const* src_tab) {
   const double scx = 1.0 / ((double)dw / (double)sw), scy = 1.0 / ((double)dh / (double)sh);
-  if (!src_tab && scx <= 1.0 && scy <= 1.0) {  // upscale: a 64x16 tile reads at most (64 + 4) x (16 + 4) source pixels
+  if (resize_cubic_f32c2_tiled(sw, sh, dw, dh, src_tab != nullptr)) {
     hipLaunchKernelGGL(k_resize_cubic_f32c2_tiled, dim3((dw + UC_TW - 1) / UC_TW, (dh + UC_TH - 1) / UC_TH, B), dim3(256),
                        0, st, src, sw, sh, sbs, dst, dw, dh, dbs, scx, scy, post_scale);
     return;

@@ -70,6 +70,11 @@ void launch_gradients(hipStream_t st, const float* I, float2* G, int w, int h, s
 void launch_blur_to_records(hipStream_t st, const float2* flow, void* rec, int w, int h, size_t bs, int B,
                             const BlurTaps& t, const float2* G, const float* A, const FlowIdx& idx,
                             unsigned* rowflags = nullptr);
+// the kernel a shape gets: one-channel planes whose 64x16 tiles' source boxes fit 76x20 floats take k_resize_linear_f32c1_tiled,
+// everything else k_resize_linear_f32; upscales (ratios <= 1) of flows given as one array take k_resize_cubic_f32c2_tiled, a
+// downscale on either axis and sources given through a pointer table k_resize_cubic_f32c2. Same results bit for bit.
+bool resize_linear_f32_tiled(int sw, int sh, int dw, int dh, int cn);
+bool resize_cubic_f32c2_tiled(int sw, int sh, int dw, int dh, bool src_tab);
 void launch_resize_linear_f32(hipStream_t st, const float* src, int sw, int sh, size_t sbs, float* dst, int dw, int dh,
                               size_t dbs, int cn, int B, float post_scale, int do_scale);
 void launch_resize_cubic_f32c2(hipStream_t st, const float2* src, int sw, int sh, size_t sbs, float2* dst, int dw,

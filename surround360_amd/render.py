@@ -213,6 +213,89 @@ class Context:
                                              _p(prev), _p(mo), C.c_float(prev_scale), C.byref(o), _p(info)))
         return out, dict(zip(_capi.FLOW_LEVEL_INFO, (int(v) for v in info)))
 
+    def debug_flow_prepare(self, images, i0, i1, prev_images=None, prev_flows=None, alg="pixflow_low", fill=0xFF, max_levels=64):
+        """The flow engine's preparation (include/s360_debug_flow_pyramid.h) on N BGRA images (N x h x w x 4) for the flows
+        i0[b] -> i1[b], optionally with N previous images and B previous flows (B x h x w x 2). Returns {"sizes": [(w, h)] finest
+        first, "gray", "alpha": per level N x h x w}, and with previous state {"prev": per level B x h x w x 2 (before the level's
+        factor), "motion": per level N x h x w, "factors": float32 per level}. fill: the byte every engine buffer the preparation
+        writes holds before it runs (None: left as the last call left them)."""
+        images = _u8(images)
+        n, h, w = images.shape[:3]
+        assert images.shape == (n, h, w, 4)
+        i0, i1 = np.ascontiguousarray(i0, np.int32), np.ascontiguousarray(i1, np.int32)
+        b = len(i0)
+        assert len(i1) == b
+        use_prev = prev_images is not None or prev_flows is not None
+        pim = _u8(prev_images).reshape(n, h, w, 4) if prev_images is not None else None
+        pfl = np.ascontiguousarray(prev_flows, np.float32).reshape(b, h, w, 2) if prev_flows is not None else None
+        # room for any pyramid of x0.9 levels: sum of 0.81^l < 5.3, plus the roundings up of max_levels levels
+        cap = 6 * max(w // 2, 1) * max(h // 2, 1) + 2 * max_levels * (w // 2 + h // 2 + 1)
+        lw, lh = np.zeros(max_levels, np.int32), np.zeros(max_levels, np.int32)
+        nl = C.c_int()
+        factors = np.zeros(max_levels, np.float32)
+        byte = 0 if fill is None else fill
+        pyr = np.full(2 * n * cap * 4, byte, np.uint8).view(np.float32)
+        prev = np.full(b * cap * 8, byte, np.uint8).view(np.float32) if use_prev else None
+        motion = np.full(n * cap * 4, byte, np.uint8).view(np.float32) if use_prev else None
+        o = _capi.FlowPrepareOut(max_levels, cap, _p(lw), _p(lh), C.cast(C.byref(nl), C.c_void_p), _p(factors), _p(pyr), _p(prev), _p(motion))
+        self._ck(lib().s360_debug_flow_prepare(self.h, _p(images), n, w, h, _p(i0), _p(i1), b, _p(pim), _p(pfl), alg.encode(),
+                                               -1 if fill is None else fill, C.byref(o)))
+        sizes = [(int(lw[k]), int(lh[k])) for k in range(nl.value)]
+        out = {"sizes": sizes, "gray": [], "alpha": []}
+        if use_prev:
+            out.update(prev=[], motion=[], factors=factors[:nl.value].copy())
+        off = 0
+        for a, c in sizes:
+            px = a * c
+            lvl = pyr[2 * n * off:2 * n * (off + px)].reshape(2, n, c, a)
+            out["gray"].append(lvl[0])
+            out["alpha"].append(lvl[1])
+            if use_prev:
+                out["prev"].append(prev[2 * b * off:2 * b * (off + px)].reshape(b, c, a, 2))
+                out["motion"].append(motion[n * off:n * (off + px)].reshape(n, c, a))
+            off += px
+        return out
+
+    def debug_resize_linear_f32(self, src, dw, dh, post_scale=1.0, do_scale=False, fill=0xFF):
+        """The pyramids' INTER_LINEAR resize (include/s360_debug_flow_pyramid.h) of B planes (B x sh x sw: one channel, or
+        B x sh x sw x 2: two interleaved) through the engine's launcher: (result, tiled kernel taken). Every byte of the result
+        is `fill` before the launch."""
+        src = np.ascontiguousarray(src, np.float32)
+        b, sh, sw = src.shape[:3]
+        cn = 1 if src.ndim == 3 else src.shape[3]
+        dst = np.full((b, dh, dw) + src.shape[3:], fill * 0x01010101, np.uint32).view(np.float32)
+        tiled = C.c_int()
+        self._ck(lib().s360_debug_resize_linear_f32(self.h, _p(src), sw, sh, cn, b, dw, dh, C.c_float(post_scale), 1 if do_scale else 0,
+                                                    _p(dst), C.cast(C.byref(tiled), C.c_void_p)))
+        return dst, bool(tiled.value)
+
+    def debug_resize_linear_f32_kernel(self, sw, sh, dw, dh, cn=1):
+        """True if the launcher takes the tiled kernel for the shape; nothing is launched."""
+        tiled = C.c_int(-1)
+        self._ck(lib().s360_debug_resize_linear_f32(self.h, None, sw, sh, cn, 1, dw, dh, C.c_float(1.0), 0, None,
+                                                    C.cast(C.byref(tiled), C.c_void_p)))
+        return bool(tiled.value)
+
+    def debug_resize_cubic_flow(self, src, dw, dh, post_scale=1.0, through_table=False, fill=0xFF):
+        """The flows' INTER_CUBIC resize and scalar multiply (include/s360_debug_flow_pyramid.h) of B flows (B x sh x sw x 2) through
+        the engine's launcher, the sources as one array or as one allocation each behind a pointer table: (result, tiled kernel
+        taken). Every byte of the result is `fill` before the launch."""
+        src = np.ascontiguousarray(src, np.float32)
+        b, sh, sw = src.shape[:3]
+        assert src.shape == (b, sh, sw, 2)
+        dst = np.full((b, dh, dw, 2), fill * 0x01010101, np.uint32).view(np.float32)
+        tiled = C.c_int()
+        self._ck(lib().s360_debug_resize_cubic_flow(self.h, _p(src), sw, sh, b, dw, dh, C.c_float(post_scale), 1 if through_table else 0,
+                                                    _p(dst), C.cast(C.byref(tiled), C.c_void_p)))
+        return dst, bool(tiled.value)
+
+    def debug_resize_cubic_flow_kernel(self, sw, sh, dw, dh, through_table=False):
+        """True if the launcher takes the tiled kernel for the shape; nothing is launched."""
+        tiled = C.c_int(-1)
+        self._ck(lib().s360_debug_resize_cubic_flow(self.h, None, sw, sh, 1, dw, dh, C.c_float(1.0), 1 if through_table else 0, None,
+                                                    C.cast(C.byref(tiled), C.c_void_p)))
+        return bool(tiled.value)
+
     def debug_remap_packed(self, src, mp, alpha_mode=0, y_feather_start=0, feather_size=1, weights=0, fill=0):
         """The frame's packed bicubic remap (include/s360_debug_remap.h) of B BGRA sources (B x sh x sw x 4) through B maps
         (B x dh x dw x 2). Returns (images B x dh x dw x 4, packed dwords B x dh x dw, tile records B x ty x tx x 4); every byte of

@@ -316,6 +316,45 @@ def pixflow_entry(i0):
     return down, I, A
 
 
+def pixflow_prepare(i0, i1, prev_flow=None, prev_i1=None):
+    """PixFlow::prepare of one pair (oracle/pixflow.h: Prepared): {"sizes": [(w, h)] finest first, "down0", "down1" (dh x dw x 4),
+    "I0", "I1", "A0", "A1": lists of levels (h x w; level 0 of I is the pre-blurred grey)}, and with previous state {"prev" (levels
+    of h x w x 2: the previous flow downscaled and x rows_down / rows_full, BEFORE the per-level scale), "motion" (h x w),
+    "factors" (float32 per level)}."""
+    i0, i1 = np.ascontiguousarray(i0, np.uint8), np.ascontiguousarray(i1, np.uint8)
+    h, w, _ = i0.shape
+    assert i1.shape == i0.shape and (prev_flow is None) == (prev_i1 is None)
+    sizes = pixflow_levels(w, h)
+    P = sum(a * b for a, b in sizes)
+    dw, dh = sizes[0]
+    use_prev = prev_flow is not None
+    pf = np.ascontiguousarray(prev_flow, np.float32).reshape(h, w, 2) if use_prev else None
+    p1 = np.ascontiguousarray(prev_i1, np.uint8).reshape(h, w, 4) if use_prev else None
+    down = [np.empty((dh, dw, 4), np.uint8) for _ in range(2)]
+    pyr = [np.empty(P, np.float32) for _ in range(4)]
+    prev = np.empty(2 * P, np.float32) if use_prev else None
+    motion = np.empty(P, np.float32) if use_prev else None
+    factors = np.empty(len(sizes), np.float32) if use_prev else None
+    fn = lib().orc_pixflow_prepare
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11
+    n = fn(_p(i0), _p(i1), w, h, _p(pf), _p(p1), _p(down[0]), _p(down[1]), _p(pyr[0]), _p(pyr[1]), _p(pyr[2]), _p(pyr[3]), _p(prev),
+           _p(motion), _p(factors))
+    assert n == len(sizes)
+
+    def split(a, c):
+        out, off = [], 0
+        for lw, lh in sizes:
+            out.append(a[off * c:(off + lw * lh) * c].reshape((lh, lw, 2) if c == 2 else (lh, lw)))
+            off += lw * lh
+        return out
+    r = {"sizes": sizes, "down0": down[0], "down1": down[1]}
+    r.update({k: split(a, 1) for k, a in zip(("I0", "I1", "A0", "A1"), pyr)})
+    if use_prev:
+        r.update(prev=split(prev, 2), motion=split(motion, 1), factors=factors)
+    return r
+
+
 def pixflow_level(I0, I1, a0, a1, flow=None, hint="UNKNOWN", search20=False):
     h, w = I0.shape
     f = np.zeros((h, w, 2), np.float32) if flow is None else np.ascontiguousarray(flow, np.float32).copy()

@@ -234,7 +234,7 @@ def test_operator_level_gpu_tests_pass_on_the_emulated_library(emu_programs):
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_ops.py"),
                         os.path.join(ROOT, "tests", "test_gpu_isp.py"), os.path.join(ROOT, "tests", "test_gpu_isp_stages.py"),
                         os.path.join(ROOT, "tests", "test_gpu_png.py"), os.path.join(ROOT, "tests", "test_gpu_flow_level.py"),
-                        os.path.join(ROOT, "tests", "test_gpu_remap_packed.py"),
+                        os.path.join(ROOT, "tests", "test_gpu_remap_packed.py"), os.path.join(ROOT, "tests", "test_gpu_flow_pyramid.py"),
                         "-q", "-m", "gpu", "-k", "not test_level_dispatch_as_production", "-p", "no:cacheprovider"],
                        capture_output=True, text=True, env=e, timeout=1800, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:]
