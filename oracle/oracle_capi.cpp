@@ -107,6 +107,18 @@ void orc_pole_warp_map(const float* flow, int extW, int rows, float poleCameraRa
   ImgF r = poleWarpMap(wrapF(flow, extW, rows, 2), R);
   std::memcpy(map, r.d.data(), r.bytes());
 }
+// convertSphericalToCubemapBicubicRemap + stackOutputCubemapFaces of two caller-made eyes of sw x sh, `c` channels (render.h:
+// stereoCubemap); video 1: "video", 0: "photo". dst: (video ? 4 : 12) * face_h x (video ? 3 : 1) * face_w x c
+void orc_stereo_cubemap(const uint8_t* eyeL, const uint8_t* eyeR, int sw, int sh, int c, int face_w, int face_h, int video, uint8_t* dst) {
+  const ImgU8 r = stereoCubemap(wrapU8(eyeL, sw, sh, c), wrapU8(eyeR, sw, sh, c), face_w, face_h, video ? "video" : "photo");
+  std::memcpy(dst, r.d.data(), r.bytes());
+}
+// the warp map of one face for an equirect of sw x sh (render.h: cubemapWarpMap); face: index in RIGHT, LEFT, TOP, BOTTOM, BACK, FRONT
+void orc_cubemap_warp_map(int face, int sw, int sh, int face_w, int face_h, float* map) {
+  static const int faces[6] = {CUBE_RIGHT, CUBE_LEFT, CUBE_TOP, CUBE_BOTTOM, CUBE_BACK, CUBE_FRONT};
+  const ImgF r = cubemapWarpMap(faces[face], sw, sh, (float)M_PI, face_w, face_h);
+  std::memcpy(map, r.d.data(), r.bytes());
+}
 void orc_remap_cubic_f32(const float* s, int sw, int sh, int c, const float* map, int dw, int dh, float* d) {
   ImgF r = remapCubicF32(wrapF(s, sw, sh, c), wrapF(map, dw, dh, 2));
   std::memcpy(d, r.d.data(), r.bytes());

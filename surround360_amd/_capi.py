@@ -119,6 +119,8 @@ FLOW_LEVEL_INFO_COUNT = 8
 DEBUG_REMAP_SYMBOLS = ["s360_debug_remap_packed", "s360_debug_pole_warp_packed", "s360_debug_remap_by_flow"]
 # ... and the ones include/s360_debug_flow_pyramid.h declares
 DEBUG_FLOW_PYRAMID_SYMBOLS = ["s360_debug_flow_prepare", "s360_debug_resize_linear_f32", "s360_debug_resize_cubic_flow"]
+# ... and the ones include/s360_debug_cubemap.h declares
+DEBUG_CUBEMAP_SYMBOLS = ["s360_debug_cubemap_tiles", "s360_debug_cubemap"]
 
 
 class FlowPrepareOut(C.Structure):
@@ -221,6 +223,10 @@ def lib():
         L.s360_debug_pole_warp_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p] * 3
         L.s360_debug_remap_by_flow.restype = C.c_int
         L.s360_debug_remap_by_flow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.s360_debug_cubemap_tiles.restype = C.c_int
+        L.s360_debug_cubemap_tiles.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 4
+        L.s360_debug_cubemap.restype = C.c_int
+        L.s360_debug_cubemap.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 2
         L.s360_isp_config_defaults.restype = None
         L.s360_isp_destroy.restype = None
         L.s360_isp_destroy.argtypes = [C.c_void_p]

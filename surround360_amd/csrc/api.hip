@@ -14,6 +14,7 @@
 #include "../../include/s360_debug_flow_level.h"
 #include "../../include/s360_debug_flow_pyramid.h"
 #include "../../include/s360_debug_isp.h"
+#include "../../include/s360_debug_cubemap.h"
 #include "../../include/s360_debug_remap.h"
 #include "ctx.hpp"
 #include "isp.hpp"
@@ -703,6 +704,54 @@ int s360_debug_remap_by_flow(s360_ctx* c, const uint8_t* src, int w, int h, cons
     launch_remap_by_flow(c->st, dsrc.as<uchar4>(), w, h, dflow.as<float2>(), ddst.as<uchar4>(), F.tab.dev);
     d2h(c, dst, ddst.p, n * 4);
   });
+}
+
+// test taps (include/s360_debug_cubemap.h): the frame's stereo cubemap launchers on caller-made eyes, through the face maps the
+// frame builds (cube_face_maps). Buffers of the call's own; the outputs are uploaded first, as above.
+static void debug_cubemap_impl(s360_ctx* c, const uint8_t* eyes, int n_slots, int sw, int sh, int fw, int fh, int video, int lds_pixels,
+                               uint8_t* out, float* maps, uint32_t* packed, int32_t* tiles, bool tiled) {
+  need(c && eyes && out && maps && (!tiled || (packed && tiles)), "null argument");
+  need(sw > 0 && sh > 0 && fw > 0 && fh > 0 && sw <= 16384 && sh <= 16384 && fw <= 16384 && fh <= 16384, "bad size");
+  need(n_slots >= 1 && n_slots <= 64, "bad number of slots");
+  need(video == 0 || video == 1, "bad format");
+  need(!tiled || lds_pixels == 4096 || lds_pixels == 2560, "the box of a tile holds 4096 or 2560 pixels");
+  FrameState& F = frame_state(c);
+  const size_t en = (size_t)sw * sh * 4, px = (size_t)6 * fw * fh, on = 2 * px * 3, nt = cubemap_tile_count(fw, fh);
+  const std::vector<float> m = cube_face_maps(sw, sh, fw, fh);
+  DevBuf deyes, dmaps, dout, dpk, dtl;
+  deyes.ensure(2 * (size_t)n_slots * en); dmaps.ensure(px * sizeof(float2)); dout.ensure((size_t)n_slots * on);
+  h2d(c, deyes.p, eyes, 2 * (size_t)n_slots * en);
+  h2d(c, dmaps.p, m.data(), px * sizeof(float2));
+  h2d(c, dout.p, out, (size_t)n_slots * on);
+  std::vector<const uchar4*> ep(2 * (size_t)n_slots);
+  std::vector<uint8_t*> op(n_slots);
+  for (size_t k = 0; k < ep.size(); ++k) ep[k] = reinterpret_cast<const uchar4*>(static_cast<const uint8_t*>(deyes.p) + k * en);
+  for (int k = 0; k < n_slots; ++k) op[k] = static_cast<uint8_t*>(dout.p) + (size_t)k * on;
+  if (tiled) {
+    dpk.ensure(px * sizeof(unsigned)); dtl.ensure(nt * 16);
+    h2d(c, dpk.p, packed, px * sizeof(unsigned));
+    h2d(c, dtl.p, tiles, nt * 16);
+    launch_cubemap_pack(c->st, dmaps.as<float2>(), sw, sh, fw, fh, video, lds_pixels, dpk.as<unsigned>(), dtl.p);
+    launch_cubemap_tiles(c->st, ep.data(), op.data(), n_slots, sw, sh, dmaps.as<float2>(), dpk.as<unsigned>(), dtl.p, fw, fh, video,
+                         lds_pixels, F.tab.dev);
+  } else {
+    for (int k = 0; k < n_slots; ++k)
+      launch_cubemap(c->st, ep[2 * k], ep[2 * k + 1], sw, sh, dmaps.as<float2>(), fw, fh, video, op[k], F.tab.dev);
+  }
+  d2h(c, out, dout.p, (size_t)n_slots * on);  // (synchronises the stream: `m` and the pointer lists live until here)
+  d2h(c, maps, dmaps.p, px * sizeof(float2));
+  if (tiled) {
+    d2h(c, packed, dpk.p, px * sizeof(unsigned));
+    d2h(c, tiles, dtl.p, nt * 16);
+  }
+}
+int s360_debug_cubemap_tiles(s360_ctx* c, const uint8_t* eyes, int n_slots, int sw, int sh, int fw, int fh, int video, int lds_pixels,
+                             uint8_t* out, float* maps, uint32_t* packed, int32_t* tiles) {
+  return guard(c, [&] { debug_cubemap_impl(c, eyes, n_slots, sw, sh, fw, fh, video, lds_pixels, out, maps, packed, tiles, true); });
+}
+int s360_debug_cubemap(s360_ctx* c, const uint8_t* eyes, int n_slots, int sw, int sh, int fw, int fh, int video, uint8_t* out,
+                       float* maps) {
+  return guard(c, [&] { debug_cubemap_impl(c, eyes, n_slots, sw, sh, fw, fh, video, 0, out, maps, nullptr, nullptr, false); });
 }
 
 int s360_spherical_warp_map(s360_ctx* c, float* map_out, int dw, int dh, const s360_camera* cam, float l, float r,

@@ -1123,6 +1123,19 @@ void cube_map_entry(float x, float y, int face, int srcCols, int srcRows, float 
 }
 }  // namespace
 
+std::vector<float> cube_face_maps(int W, int H, int fw, int fh) {
+  static const int faces[6] = {CUBE_RIGHT, CUBE_LEFT, CUBE_TOP, CUBE_BOTTOM, CUBE_BACK, CUBE_FRONT};
+  std::vector<float> m((size_t)6 * fw * fh * 2);
+  const float dy = 1.0f / float(fw), dx = 1.0f / float(fh);
+  for (int f = 0; f < 6; ++f)
+    for (int j = 0; j < fh; ++j)
+      for (int i = 0; i < fw; ++i) {
+        float* e = &m[(((size_t)f * fh + j) * fw + i) * 2];
+        cube_map_entry(float(i) * dy - 0.5f, float(j) * dx - 0.5f, faces[f], W, H, (float)M_PI, e, e + 1);
+      }
+  return m;
+}
+
 s360_ctx::CubeMaps& cube_maps(s360_ctx* c, int fw, int fh, int video) {
   if (fw <= 0 || fh <= 0) throw Error(S360_ERR_INVALID_ARG, "cubemap face size must be positive");
   const int W = c->P.eqr_width, H = c->P.eqr_height;
@@ -1130,15 +1143,7 @@ s360_ctx::CubeMaps& cube_maps(s360_ctx* c, int fw, int fh, int video) {
   for (auto& e : c->cubeMaps)
     if (e->fw == fw && e->fh == fh && e->W == W && e->H == H) M = e.get();
   if (!M) {
-    static const int faces[6] = {CUBE_RIGHT, CUBE_LEFT, CUBE_TOP, CUBE_BOTTOM, CUBE_BACK, CUBE_FRONT};
-    std::vector<float> m((size_t)6 * fw * fh * 2);
-    const float dy = 1.0f / float(fw), dx = 1.0f / float(fh);
-    for (int f = 0; f < 6; ++f)
-      for (int j = 0; j < fh; ++j)
-        for (int i = 0; i < fw; ++i) {
-          float* e = &m[(((size_t)f * fh + j) * fw + i) * 2];
-          cube_map_entry(float(i) * dy - 0.5f, float(j) * dx - 0.5f, faces[f], W, H, (float)M_PI, e, e + 1);
-        }
+    const std::vector<float> m = cube_face_maps(W, H, fw, fh);
     auto n = std::make_unique<s360_ctx::CubeMaps>();
     n->maps.ensure(m.size() * sizeof(float));
     S360_HIP(hipMemcpyAsync(n->maps.p, m.data(), m.size() * sizeof(float), hipMemcpyHostToDevice, c->st_user));

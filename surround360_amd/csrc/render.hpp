@@ -145,6 +145,9 @@ void frame_cubemap(s360_ctx* c, int face_w, int face_h, bool video, int* ow, int
 // the context's face maps for (face size, eye size), with their prepared form for `video` (0 / 1) when video >= 0: built on
 // first use (host arithmetic, upload, pack kernel, host wait), then shared by every slot and stream
 s360_ctx::CubeMaps& cube_maps(s360_ctx* c, int face_w, int face_h, int video);
+// ... and their host arithmetic alone: 6 x face_h x face_w x 2 floats for eyes of W x H (what cube_maps uploads; the test tap of
+// include/s360_debug_cubemap.h builds its own through it)
+std::vector<float> cube_face_maps(int W, int H, int face_w, int face_h);
 
 // RCCL strip gather of the sharded frame (comm.cpp)
 void comm_unique_id(void* id128);

@@ -333,6 +333,35 @@ class Context:
         self._ck(lib().s360_debug_remap_by_flow(self.h, _p(src), w, h, _p(fl), _p(dst)))
         return dst
 
+    def debug_cubemap_tiles(self, eyes, fw, fh, fmt="video", lds_pixels=4096, fill=0):
+        """The cubemap of every frame (include/s360_debug_cubemap.h) of S pairs of BGRA eyes (S x 2 x sh x sw x 4) through the
+        frame's map construction and launchers. Returns (stacked BGR cubemaps S x oh x ow x 3, face maps 6 x fh x fw x 2, packed
+        dwords of one eye's half oh / 2 x ow, tile records 6 x ty x tx x 4); every byte of the four is `fill` before the launches."""
+        eyes = _u8(eyes)
+        s, two, sh, sw = eyes.shape[:4]
+        assert eyes.shape == (s, 2, sh, sw, 4)
+        video = {"video": 1, "photo": 0}[fmt]
+        ow, oh = (3 * fw, 4 * fh) if video else (fw, 12 * fh)
+        out = np.full((s, oh, ow, 3), fill, np.uint8)
+        maps = np.full((6, fh, fw, 2), fill * 0x01010101, np.uint32).view(np.float32)
+        packed = np.full((oh // 2, ow), fill * 0x01010101, np.uint32)
+        tiles = np.full((6, -(-fh // 16), -(-fw // 16), 4), fill * 0x01010101, np.uint32).view(np.int32)
+        self._ck(lib().s360_debug_cubemap_tiles(self.h, _p(eyes), s, sw, sh, fw, fh, video, lds_pixels, _p(out), _p(maps), _p(packed),
+                                                _p(tiles)))
+        return out, maps, packed, tiles
+
+    def debug_cubemap(self, eyes, fw, fh, fmt="video", fill=0):
+        """The on-demand cubemap kernel (one thread per pixel) on the same eyes and maps: (stacked BGR cubemaps, face maps)."""
+        eyes = _u8(eyes)
+        s, two, sh, sw = eyes.shape[:4]
+        assert eyes.shape == (s, 2, sh, sw, 4)
+        video = {"video": 1, "photo": 0}[fmt]
+        ow, oh = (3 * fw, 4 * fh) if video else (fw, 12 * fh)
+        out = np.full((s, oh, ow, 3), fill, np.uint8)
+        maps = np.full((6, fh, fw, 2), fill * 0x01010101, np.uint32).view(np.float32)
+        self._ck(lib().s360_debug_cubemap(self.h, _p(eyes), s, sw, sh, fw, fh, video, _p(out), _p(maps)))
+        return out, maps
+
     def spherical_warp_map(self, cam, dw, dh, l, r, t, b):
         m = np.empty((dh, dw, 2), np.float32)
         self._ck(lib().s360_spherical_warp_map(self.h, _p(m), dw, dh, C.byref(cam), C.c_float(l), C.c_float(r),

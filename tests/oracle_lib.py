@@ -160,6 +160,25 @@ def pole_warp_map(flow, pole_camera_radius, phi_ramp_start, phi_mid):
     return m
 
 
+def stereo_cubemap(eye_l, eye_r, face_w, face_h, fmt="video"):
+    """stereoCubemap (convertSphericalToCubemapBicubicRemap + stackOutputCubemapFaces, both eyes stacked) of two caller-made eyes
+    (sh x sw x c, uint8)."""
+    a, b = np.ascontiguousarray(eye_l, np.uint8), np.ascontiguousarray(eye_r, np.uint8)
+    sh, sw, c = a.shape
+    assert b.shape == a.shape
+    video = {"video": 1, "photo": 0}[fmt]
+    d = np.empty(((4 if video else 12) * face_h, (3 if video else 1) * face_w, c), np.uint8)
+    lib().orc_stereo_cubemap(_p(a), _p(b), sw, sh, c, face_w, face_h, video, _p(d))
+    return d
+
+
+def cubemap_warp_map(face, sw, sh, face_w, face_h):
+    """cubemapWarpMap of one face (index in RIGHT, LEFT, TOP, BOTTOM, BACK, FRONT) for an equirect of sw x sh: face_h x face_w x 2."""
+    m = np.empty((face_h, face_w, 2), np.float32)
+    lib().orc_cubemap_warp_map(face, sw, sh, face_w, face_h, _p(m))
+    return m
+
+
 def remap_cubic_f32(src, mp):
     s = _f3(src)
     mp = np.ascontiguousarray(mp, np.float32)

@@ -25,6 +25,22 @@ def test_library_exports_every_declared_symbol(s360lib):
     assert sorted(_capi.SYMBOLS) == names, "python binding list out of sync with include/s360.h"
 
 
+def test_cubemap_test_taps_are_declared_listed_and_exported(s360lib):
+    """include/s360_debug_cubemap.h: a header of its own (include/s360.h does not include it), plain C, its symbols listed by the
+    binding and exported by the library."""
+    import subprocess
+    from surround360_amd import _capi
+    hdr = os.path.join(ROOT, "include", "s360_debug_cubemap.h")
+    src = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(s360_[a-z0-9_]+)\s*\(", src)))
+    assert names == sorted(_capi.DEBUG_CUBEMAP_SYMBOLS) == ["s360_debug_cubemap", "s360_debug_cubemap_tiles"]
+    assert not set(names) & set(header_symbols())
+    for n in names:
+        assert hasattr(s360lib, n), "libs360.so does not export " + n
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", "-x", "c", hdr])
+    subprocess.check_call(["g++", "-std=c++11", "-Wall", "-Werror", "-fsyntax-only", "-x", "c++", hdr])
+
+
 def test_version_and_device_count(s360lib):
     assert b"gfx950" in s360lib.s360_version()
     assert s360lib.s360_device_count() >= 0

@@ -227,7 +227,9 @@ def test_operator_level_gpu_tests_pass_on_the_emulated_library(emu_programs):
     tests/test_gpu_png.py (the device PNG encoder against libpng / zlib) and tests/test_gpu_flow_level.py (one pyramid level of the
     flow engine stage by stage, its forced variants included; its hardware-only production-dispatch cases are deselected by name,
     so that nothing of the replay may skip) and tests/test_gpu_remap_packed.py (the frame's packed bicubic remap, the pole warp and
-    pole removal's warp on caller-made maps: pixels, packed coordinates and tile records word for word), unchanged, in a
+    pole removal's warp on caller-made maps: pixels, packed coordinates and tile records word for word) and
+    tests/test_gpu_cubemap_tiles.py (the stereo cubemap's pack / tile kernels on caller-made eyes: maps, records, dwords, pixels of
+    every slot), unchanged, in a
     process whose Python binding points at the emulated library (tests/conftest.py: S360_TEST_EMULATED_LIB=1)."""
     import sys
     e = dict(os.environ, S360_TEST_EMULATED_LIB="1")
@@ -235,6 +237,7 @@ def test_operator_level_gpu_tests_pass_on_the_emulated_library(emu_programs):
                         os.path.join(ROOT, "tests", "test_gpu_isp.py"), os.path.join(ROOT, "tests", "test_gpu_isp_stages.py"),
                         os.path.join(ROOT, "tests", "test_gpu_png.py"), os.path.join(ROOT, "tests", "test_gpu_flow_level.py"),
                         os.path.join(ROOT, "tests", "test_gpu_remap_packed.py"), os.path.join(ROOT, "tests", "test_gpu_flow_pyramid.py"),
+                        os.path.join(ROOT, "tests", "test_gpu_cubemap_tiles.py"),
                         "-q", "-m", "gpu", "-k", "not test_level_dispatch_as_production", "-p", "no:cacheprovider"],
                        capture_output=True, text=True, env=e, timeout=1800, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-3000:]

@@ -81,6 +81,37 @@ def test_single_frame(env, fmt, fw, fh, sharpening):
         ctx.close()
 
 
+# ---- the smallest frames --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt,fw,fh", [("video", 33, 17), ("photo", 16, 16)])
+@pytest.mark.parametrize("eqr_w,eqr_h", [(28, 14), (42, 21)])
+def test_smallest_frames(tmp_path, rig_json, oracle, s360lib, eqr_w, eqr_h, fmt, fw, fh):
+    """The smallest frames s360_create accepts (the flags of test_gpu_ops.py::test_tiny_frames_equal_the_oracle) into faces larger
+    than the eyes: the boxes of the tiles around the poles are in LDS and wrap in y (tests/test_gpu_cubemap_tiles.py counts them).
+    The cubemap rendered with the frame == the oracle's == the on-demand call's."""
+    cam = 64
+    path = rigutil.scaled_rig_json(rig_json, str(tmp_path / "rig_tiny.json"), cam / 2048.0)
+    side, top, bottom = rigutil.frame_inputs(path, cam)
+    flags = dict(eqr_width=eqr_w, eqr_height=eqr_h, enable_top=1, enable_bottom=1, final_eqr_width=0, final_eqr_height=0,
+                 sharpening=0.25, side_alpha_feather_size=7, std_alpha_feather_size=3)
+    cams, _ = oracle.load_rig(path)
+    of = oracle.Frame(cams, oracle.make_params(**flags))
+    want_eq, _ = of.render(side, top, bottom)
+    want = of.cubemap(fw, fh, fmt)
+    ctx = R.Context(R.RigDescription(path), R.make_params(**flags))
+    try:
+        ctx.set_cubemap_output(fw, fh, fmt)
+        assert ctx.cubemap_size() == (want.shape[1], want.shape[0], 3)
+        ctx.upload_frame(side, top, bottom)
+        ctx.render()
+        got = ctx.download_cubemap()
+        _cmp("cubemap with the frame", got, want)
+        _cmp("on-demand cubemap", ctx.cubemap(fw, fh, fmt), got)
+        _cmp("equirect", ctx.download_equirect(), want_eq)
+        assert got.std() > 5
+    finally:
+        ctx.close()
+
+
 # ---- batches --------------------------------------------------------------------------------------------------------
 def test_batch_of_three_slots_and_a_subset(env):
     """Three slots with different inputs through render_batch: every slot's cubemap equals that slot rendered alone;
