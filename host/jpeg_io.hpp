@@ -15,6 +15,7 @@
 // above). An OpenCV built with its bundled IJG libjpeg 9 upsamples chroma by DCT scaling and yields different pixels for
 // subsampled files; nothing here reproduces that.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -485,6 +486,284 @@ inline pngio::Image decode_any(const std::vector<uint8_t>& file, const std::stri
   pngio::Image im;
   pngio::decode_into(file, path, keep_alpha, im);
   return im;
+}
+
+// ---- baseline JPEG writer ---------------------------------------------------------------------------------------------
+// What cv::imwrite(path, bgr) writes through libjpeg at OpenCV's defaults (quality 95; the reference's TestHyperPreview saves
+// its preview frames this way, TestHyperPreview.cpp:160), restated so that the quantised coefficients are the same:
+//   * baseline sequential, one interleaved scan, JFIF 1.01 APP0 (no density), markers in libjpeg's order: SOI, APP0, DQT x 2,
+//     SOF0, DHT x 4, SOS;
+//   * quality 95 through jpeg_quality_scaling (scale factor 10) of the Annex K tables, clamped to 1..255;
+//   * RGB -> YCbCr with libjpeg's 16-bit fixed-point tables (jccolor.c), 4:2:0: h2v2 downsampling with the alternating bias
+//     1, 2, 1, 2 (jcsample.c), the right edge and the bottom row replicated up to whole blocks (expand_right_edge, jcprepct.c),
+//     dummy blocks past a component's last block — zero AC, the DC of the block before (jccoefct.c);
+//   * the integer "islow" forward DCT (jfdctint.c: 13-bit constants, 2 extra bits between the passes), libjpeg's
+//     quantisation rounding (jcdctmgr.c: half the divisor added to the magnitude, truncating division);
+//   * the standard Huffman tables of Annex K (jcparam.c), 0xFF bytes stuffed, the last byte padded with 1-bits.
+// tests/test_cpu_preview.py: PIL decodes these files to exactly the pixels it decodes from its own save(quality=95,
+// subsampling=2) of the same image, i.e. the quantised coefficients are equal. Runs on the host: the bitstream is serial.
+namespace enc_detail {
+static const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+static const uint8_t kLumQ[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40, 57,
+                                  69, 56, 14, 17, 22,  29,  51,  87,  80, 62, 18, 22, 37,  56,  68,  109, 103, 77, 24, 35, 55, 64,
+                                  81, 104, 113, 92, 49, 64,  78,  87,  103, 121, 120, 101, 72, 92,  95,  98,  112, 100, 103, 99};
+static const uint8_t kChrQ[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
+                                  99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
+                                  99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+static const uint8_t kDcLumBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
+static const uint8_t kDcChrBits[16] = {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0};
+static const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+static const uint8_t kAcLumBits[16] = {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d};
+static const uint8_t kAcLumVals[162] = {
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
+    0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
+    0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
+    0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
+    0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
+    0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+static const uint8_t kAcChrBits[16] = {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77};
+static const uint8_t kAcChrVals[162] = {
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
+    0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
+    0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
+    0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
+    0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
+    0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
+    0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
+    0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
+
+struct EncTable {  // code and length per symbol (jchuff.c: jpeg_make_c_derived_tbl)
+  uint16_t code[256];
+  uint8_t len[256];
+  EncTable(const uint8_t* bits, const uint8_t* vals) {
+    std::memset(code, 0, sizeof code);
+    std::memset(len, 0, sizeof len);
+    unsigned c = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l) {
+      for (int i = 0; i < bits[l - 1]; ++i, ++k) {
+        code[vals[k]] = (uint16_t)c++;
+        len[vals[k]] = (uint8_t)l;
+      }
+      c <<= 1;
+    }
+  }
+};
+
+// jpeg_fdct_islow (jfdctint.c), in place on 64 ints; results are scaled up by 8
+inline void fdct_islow(int* data) {
+  const int CB = 13, P1 = 2;
+  const long F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633, F1501 = 12299, F1847 = 15137,
+             F1961 = 16069, F2053 = 16819, F2562 = 20995, F3072 = 25172;
+  auto descale = [](long x, int n) { return (int)((x + (1L << (n - 1))) >> n); };
+  for (int pass = 0; pass < 2; ++pass) {
+    const int step = pass == 0 ? 1 : 8, next = pass == 0 ? 8 : 1;  // pass 0: rows, pass 1: columns
+    for (int k = 0; k < 8; ++k) {
+      int* d = data + k * next;
+      const long t0 = d[0] + d[7 * step], t7 = d[0] - d[7 * step], t1 = d[step] + d[6 * step], t6 = d[step] - d[6 * step];
+      const long t2 = d[2 * step] + d[5 * step], t5 = d[2 * step] - d[5 * step], t3 = d[3 * step] + d[4 * step],
+                 t4 = d[3 * step] - d[4 * step];
+      const long t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+      if (pass == 0) {
+        d[0] = (int)((t10 + t11) * (1 << P1));
+        d[4 * step] = (int)((t10 - t11) * (1 << P1));
+      } else {
+        d[0] = descale(t10 + t11, P1);
+        d[4 * step] = descale(t10 - t11, P1);
+      }
+      const int sh = pass == 0 ? CB - P1 : CB + P1;
+      long z1 = (t12 + t13) * F0541;
+      d[2 * step] = descale(z1 + t13 * F0765, sh);
+      d[6 * step] = descale(z1 + t12 * (-F1847), sh);
+      z1 = t4 + t7;
+      long z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+      const long z5 = (z3 + z4) * F1175;
+      const long m4 = t4 * F0298, m5 = t5 * F2053, m6 = t6 * F3072, m7 = t7 * F1501;
+      z1 *= -F0899;
+      z2 *= -F2562;
+      z3 *= -F1961;
+      z4 *= -F0390;
+      z3 += z5;
+      z4 += z5;
+      d[7 * step] = descale(m4 + z1 + z3, sh);
+      d[5 * step] = descale(m5 + z2 + z4, sh);
+      d[3 * step] = descale(m6 + z2 + z3, sh);
+      d[step] = descale(m7 + z1 + z4, sh);
+    }
+  }
+}
+
+struct BitWriter {
+  std::vector<uint8_t>& out;
+  uint32_t acc = 0;
+  int n = 0;
+  explicit BitWriter(std::vector<uint8_t>& o) : out(o) {}
+  void put(unsigned code, int len) {
+    acc = (acc << len) | (code & ((1u << len) - 1));
+    n += len;
+    while (n >= 8) {
+      const uint8_t b = (uint8_t)(acc >> (n - 8));
+      out.push_back(b);
+      if (b == 0xFF) out.push_back(0);
+      n -= 8;
+    }
+  }
+  void flush() {
+    if (n) put(0x7F, 8 - n);  // the partial byte filled with 1-bits
+  }
+};
+}  // namespace enc_detail
+
+// bgr: h rows of w pixels, 3 bytes each (B,G,R), rows contiguous. Returns the file.
+inline std::vector<uint8_t> encode(const uint8_t* bgr, int w, int h, int quality = 95) {
+  using namespace enc_detail;
+  if (w <= 0 || h <= 0 || w > 65535 || h > 65535) throw std::runtime_error("jpeg: image size outside 1..65535");
+  if (quality < 1) quality = 1;
+  if (quality > 100) quality = 100;
+  const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2;  // jpeg_quality_scaling
+  int q[2][64];
+  for (int t = 0; t < 2; ++t)
+    for (int i = 0; i < 64; ++i) {
+      long v = ((long)(t ? kChrQ[i] : kLumQ[i]) * scale + 50L) / 100L;
+      q[t][i] = (int)(v <= 0 ? 1 : v > 255 ? 255 : v);  // force_baseline
+    }
+  // geometry: MCU 16 x 16; Y in whole blocks, chroma in whole blocks of the halved (rounded up) size
+  const int mcux = (w + 15) / 16, mcuy = (h + 15) / 16;
+  const int ybw = (w + 7) / 8, ybh = (h + 7) / 8;               // Y: blocks that exist
+  const int cw = (w + 1) / 2, ch = (h + 1) / 2;
+  const int cbw = (cw + 7) / 8, cbh = (ch + 7) / 8;             // chroma: blocks that exist
+  const int yW = ybw * 8, yH = ybh * 8, cW = cbw * 8, cH = cbh * 8;
+  const int fW = std::max(yW, cW * 2), fH = std::max(yH, ch * 2);  // full-resolution planes: right edge and bottom row replicated
+  std::vector<uint8_t> Y((size_t)fW * fH), Cb((size_t)fW * fH), Cr((size_t)fW * fH);
+  const int SB = 16, HALF = 1 << (SB - 1);
+  auto FIX = [](double x) { return (long)(x * 65536.0 + 0.5); };
+  const long ry = FIX(0.29900), gy = FIX(0.58700), by = FIX(0.11400), rcb = -FIX(0.16874), gcb = -FIX(0.33126), bcb = FIX(0.50000),
+             gcr = -FIX(0.41869), bcr = -FIX(0.08131), off = (128L << SB) + HALF - 1;
+  for (int y = 0; y < fH; ++y) {
+    const uint8_t* row = bgr + (size_t)(y < h ? y : h - 1) * w * 3;  // expand_bottom_edge (row group, then iMCU row)
+    uint8_t *py = &Y[(size_t)y * fW], *pb = &Cb[(size_t)y * fW], *pr = &Cr[(size_t)y * fW];
+    for (int x = 0; x < fW; ++x) {
+      const uint8_t* p = row + (size_t)(x < w ? x : w - 1) * 3;      // expand_right_edge
+      const long b = p[0], g = p[1], r = p[2];
+      py[x] = (uint8_t)((ry * r + gy * g + by * b + HALF) >> SB);
+      pb[x] = (uint8_t)((rcb * r + gcb * g + bcb * b + off) >> SB);
+      pr[x] = (uint8_t)((bcb * r + gcr * g + bcr * b + off) >> SB);
+    }
+  }
+  // h2v2_downsample; the downsampled rows below the last one repeat it up to whole blocks
+  std::vector<uint8_t> cbs((size_t)cW * cH), crs((size_t)cW * cH);
+  for (int y = 0; y < cH; ++y) {
+    const int sy = y < ch ? y : ch - 1;
+    for (int c = 0; c < 2; ++c) {
+      const uint8_t* r0 = (c ? Cr : Cb).data() + (size_t)(2 * sy) * fW;
+      const uint8_t* r1 = r0 + fW;
+      uint8_t* o = (c ? crs : cbs).data() + (size_t)y * cW;
+      int bias = 1;
+      for (int x = 0; x < cW; ++x) {
+        o[x] = (uint8_t)((r0[2 * x] + r0[2 * x + 1] + r1[2 * x] + r1[2 * x + 1] + bias) >> 2);
+        bias ^= 3;
+      }
+    }
+  }
+  std::vector<uint8_t> out;
+  out.reserve((size_t)w * h / 2 + 1024);
+  auto put16 = [&](int v) { out.push_back((uint8_t)(v >> 8)); out.push_back((uint8_t)v); };
+  const uint8_t app0[] = {0xFF, 0xD8, 0xFF, 0xE0, 0, 16, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+  out.insert(out.end(), app0, app0 + sizeof app0);
+  for (int t = 0; t < 2; ++t) {
+    out.push_back(0xFF); out.push_back(0xDB); put16(67); out.push_back((uint8_t)t);
+    for (int i = 0; i < 64; ++i) out.push_back((uint8_t)q[t][kZigzag[i]]);
+  }
+  out.push_back(0xFF); out.push_back(0xC0); put16(17); out.push_back(8); put16(h); put16(w); out.push_back(3);
+  const uint8_t comps[9] = {1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1};
+  out.insert(out.end(), comps, comps + 9);
+  const uint8_t* bitsOf[4] = {kDcLumBits, kAcLumBits, kDcChrBits, kAcChrBits};
+  const uint8_t* valsOf[4] = {kDcVals, kAcLumVals, kDcVals, kAcChrVals};
+  const int nvals[4] = {12, 162, 12, 162};
+  const uint8_t ids[4] = {0x00, 0x10, 0x01, 0x11};
+  for (int t = 0; t < 4; ++t) {
+    out.push_back(0xFF); out.push_back(0xC4); put16(2 + 1 + 16 + nvals[t]); out.push_back(ids[t]);
+    out.insert(out.end(), bitsOf[t], bitsOf[t] + 16);
+    out.insert(out.end(), valsOf[t], valsOf[t] + nvals[t]);
+  }
+  const uint8_t sos[] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
+  out.insert(out.end(), sos, sos + sizeof sos);
+
+  const EncTable dcT[2] = {EncTable(kDcLumBits, kDcVals), EncTable(kDcChrBits, kDcVals)};
+  const EncTable acT[2] = {EncTable(kAcLumBits, kAcLumVals), EncTable(kAcChrBits, kAcChrVals)};
+  BitWriter bw(out);
+  int lastDc[3] = {0, 0, 0};
+  // one block: samples -> quantised coefficients (natural order). exists == false: a dummy block (zero AC, DC of `prev`)
+  auto make_block = [&](const uint8_t* plane, int stride, int bx, int by, int tq, int* coef) {
+    int d[64];
+    for (int r = 0; r < 8; ++r)
+      for (int c = 0; c < 8; ++c) d[r * 8 + c] = (int)plane[(size_t)(by * 8 + r) * stride + bx * 8 + c] - 128;
+    fdct_islow(d);
+    for (int i = 0; i < 64; ++i) {
+      const int qv = q[tq][i] << 3;
+      int t = d[i];
+      if (t < 0) { t = -t; t += qv >> 1; t = t >= qv ? t / qv : 0; t = -t; }
+      else { t += qv >> 1; t = t >= qv ? t / qv : 0; }
+      coef[i] = t;
+    }
+  };
+  auto emit_block = [&](const int* coef, int comp) {
+    const int t = comp ? 1 : 0;
+    int diff = coef[0] - lastDc[comp];
+    lastDc[comp] = coef[0];
+    int mag = diff < 0 ? -diff : diff, nb = 0;
+    while (mag) { ++nb; mag >>= 1; }
+    bw.put(dcT[t].code[nb], dcT[t].len[nb]);
+    if (nb) bw.put((unsigned)(diff < 0 ? diff - 1 : diff), nb);
+    int run = 0;
+    for (int k = 1; k < 64; ++k) {
+      const int v = coef[kZigzag[k]];
+      if (!v) { ++run; continue; }
+      while (run > 15) { bw.put(acT[t].code[0xF0], acT[t].len[0xF0]); run -= 16; }
+      int m = v < 0 ? -v : v, n = 0;
+      while (m) { ++n; m >>= 1; }
+      const int sym = (run << 4) | n;
+      bw.put(acT[t].code[sym], acT[t].len[sym]);
+      bw.put((unsigned)(v < 0 ? v - 1 : v), n);
+      run = 0;
+    }
+    if (run) bw.put(acT[t].code[0], acT[t].len[0]);
+  };
+  int coef[64], prevDc = 0;
+  for (int my = 0; my < mcuy; ++my)
+    for (int mx = 0; mx < mcux; ++mx) {
+      for (int comp = 0; comp < 3; ++comp) {
+        const int n = comp ? 1 : 2;  // blocks per MCU in each direction
+        const uint8_t* plane = comp == 0 ? Y.data() : comp == 1 ? cbs.data() : crs.data();
+        const int stride = comp ? cW : fW, bwid = comp ? cbw : ybw, bhei = comp ? cbh : ybh;
+        for (int j = 0; j < n; ++j)
+          for (int i = 0; i < n; ++i) {
+            const int bx = mx * n + i, by = my * n + j;
+            if (bx < bwid && by < bhei) {
+              make_block(plane, stride, bx, by, comp ? 1 : 0, coef);
+            } else {  // dummy block: the DC of the block before it in the MCU
+              std::memset(coef, 0, sizeof coef);
+              coef[0] = prevDc;
+            }
+            prevDc = coef[0];
+            emit_block(coef, comp);
+          }
+      }
+    }
+  bw.flush();
+  out.push_back(0xFF); out.push_back(0xD9);
+  return out;
+}
+
+inline void write(const std::string& path, const uint8_t* bgr, int w, int h, int quality = 95) {
+  const std::vector<uint8_t> file = encode(bgr, w, h, quality);
+  pngio::OutFile f(path);
+  f.put(file.data(), file.size());
+  f.close();
 }
 
 }  // namespace jpegio

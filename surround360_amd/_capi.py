@@ -121,6 +121,12 @@ DEBUG_REMAP_SYMBOLS = ["s360_debug_remap_packed", "s360_debug_pole_warp_packed",
 DEBUG_FLOW_PYRAMID_SYMBOLS = ["s360_debug_flow_prepare", "s360_debug_resize_linear_f32", "s360_debug_resize_cubic_flow"]
 # ... and the ones include/s360_debug_cubemap.h declares
 DEBUG_CUBEMAP_SYMBOLS = ["s360_debug_cubemap_tiles", "s360_debug_cubemap"]
+# ... and the ones include/s360_preview.h declares (a header of its own: pole-camera previews from packed capture frames)
+PREVIEW_SYMBOLS = ["s360_preview_create", "s360_preview_destroy", "s360_preview_cameras", "s360_preview_render_packed",
+                   "s360_preview_submit_packed", "s360_preview_fetch", "s360_preview_last_times"]
+# ... and its test taps, include/s360_debug_preview.h
+DEBUG_PREVIEW_SYMBOLS = ["s360_debug_preview_camera", "s360_debug_preview_map", "s360_debug_preview_set_maps",
+                         "s360_debug_preview_developed", "s360_debug_preview_remapped"]
 
 
 class FlowPrepareOut(C.Structure):
@@ -227,6 +233,20 @@ def lib():
         L.s360_debug_cubemap_tiles.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 4
         L.s360_debug_cubemap.restype = C.c_int
         L.s360_debug_cubemap.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 2
+        L.s360_preview_create.restype = C.c_int
+        L.s360_preview_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p] + [C.c_int] * 6 + [C.c_double] * 2
+        L.s360_preview_destroy.restype = None
+        L.s360_preview_destroy.argtypes = [C.c_void_p]
+        L.s360_preview_cameras.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.s360_preview_render_packed.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+        L.s360_preview_submit_packed.argtypes = [C.c_void_p] * 4 + [C.c_int]
+        L.s360_preview_fetch.argtypes = [C.c_void_p, C.c_void_p]
+        L.s360_preview_last_times.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.s360_debug_preview_camera.argtypes = [C.c_void_p, C.c_int, C.POINTER(Camera)]
+        L.s360_debug_preview_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.s360_debug_preview_set_maps.argtypes = [C.c_void_p] * 4
+        L.s360_debug_preview_developed.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.s360_debug_preview_remapped.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.s360_isp_config_defaults.restype = None
         L.s360_isp_destroy.restype = None
         L.s360_isp_destroy.argtypes = [C.c_void_p]

@@ -23,6 +23,10 @@
 using namespace s360;
 
 static thread_local std::string g_err;
+namespace s360 {
+// for the objects whose entry points live in files of their own (preview.hip): the calling thread's last error
+void set_thread_error(const std::string& m) { g_err = m; }
+}  // namespace s360
 
 // live contexts by uid
 namespace {

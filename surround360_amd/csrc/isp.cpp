@@ -3,6 +3,8 @@
 // buffers, one frame = upload, 5-8 kernels, download. Reference: surround360_render/source/camera_isp/CameraIsp.h.
 #include "isp.hpp"
 
+#include "expf_glibc.hpp"
+
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -334,14 +336,8 @@ void isp_init(s360_isp* o, int device, const s360_isp_config& cfg) {
   S360_HIP(hipStreamCreateWithFlags(&o->st, hipStreamNonBlocking));
   o->dLut.ensure(o->lut.size() * sizeof(float));
   S360_HIP(hipMemcpyAsync(o->dLut.p, o->lut.data(), o->lut.size() * sizeof(float), hipMemcpyHostToDevice, o->st));
-  // 2^(i/32) bit patterns minus i << 47 (the table of glibc's expf, see isp_kernels.hip)
-  unsigned long long tab[32];
-  for (int i = 0; i < 32; ++i) {
-    const double v = exp2((double)i / 32);
-    unsigned long long u;
-    std::memcpy(&u, &v, 8);
-    tab[i] = u - ((unsigned long long)i << 47);
-  }
+  unsigned long long tab[32];  // the table of glibc's expf (expf_glibc.hpp)
+  expf_glibc_table(tab);
   if (cfg.pipe) {
     isp_derive_pipe(cfg, o->dev, o->pipe);
     std::vector<unsigned short> tt(o->lut.size());  // `const int r = toneCurveLut[i][0]` into the 8- / 16-bit table (CameraIspPipe.h:67-81)

@@ -18,6 +18,7 @@
 #include "isp.hpp"
 
 #include "devmath.hpp"
+#include "expf_glibc.hpp"
 
 namespace s360 {
 
@@ -32,35 +33,7 @@ __device__ __forceinline__ float bilerpf(float x00, float x01, float x10, float 
 __device__ __forceinline__ bool is_red(const IspDev& d, int i, int j) { return (d.redMask >> ((i & 1) * 2 + (j & 1))) & 1; }
 __device__ __forceinline__ bool is_green(const IspDev& d, int i, int j) { return (d.greenMask >> ((i & 1) * 2 + (j & 1))) & 1; }
 
-// expf as glibc 2.35 computes it on x86-64 with FMA (sysdeps/ieee754/flt-32/e_expf.c through the multiarch FMA
-// build): double arithmetic, 32-entry 2^(i/32) table, cubic in double, with the contractions gcc -mfma makes.
-// tools/expf_check.c compares this sequence with the host's expf for every float <= 0 (2 139 095 041 values): no
-// difference. Only arguments <= 0 occur (noise coring). The table is built on the host with exp2().
-__device__ __forceinline__ float expf_glibc_neg(float x, const unsigned long long* __restrict__ tab) {
-  const unsigned ux = __float_as_uint(x);
-  const unsigned abstop = (ux >> 20) & 0x7ff;
-  if (abstop >= (0x42b00000u >> 20)) {  // |x| >= 88 or NaN
-    if (ux == 0xff800000u) return 0.0f;
-    if (abstop >= (0x7f800000u >> 20)) return x + x;
-    if (x < -0x1.9fe368p6f) return 0.0f;      // underflow
-    if (x < -0x1.9d1d9ep6f) return 0x1p-149f;  // __math_may_uflowf
-  }
-  const double kInvLn2N = 0x1.71547652b82fep+0 * 32, kShift = 0x1.8p+52;
-  const double C0 = 0x1.c6af84b912394p-5 / 32 / 32 / 32, C1 = 0x1.ebfce50fac4f3p-3 / 32 / 32, C2 = 0x1.62e42ff0c52d6p-1 / 32;
-  const double xd = (double)x;
-  double kd = __builtin_fma(kInvLn2N, xd, kShift);
-  const unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
-  kd -= kShift;
-  const double r = __builtin_fma(kInvLn2N, xd, -kd);
-  const unsigned long long t = tab[ki & 31] + (ki << (52 - 5));
-  const double s = __longlong_as_double((long long)t);
-  const double z = __builtin_fma(C0, r, C1);
-  const double r2 = r * r;
-  double y = __builtin_fma(C2, r, 1.0);
-  y = __builtin_fma(z, r2, y);
-  y = y * s;
-  return (float)y;
-}
+// the exact expf of the noise coring: expf_glibc (expf_glibc.hpp), arguments <= 0 only
 
 }  // namespace
 
@@ -533,7 +506,7 @@ __global__ __launch_bounds__(256) void k_isp_finish(const float* __restrict__ im
     if (SHARPEN) {
       const float l = lp[p * 3 + k];
       const float hp = v - l;
-      const float ng = 1.0f - expf_glibc_neg(-((hp * hp) * d.noiseCore), exptab);
+      const float ng = 1.0f - expf_glibc(-((hp * hp) * d.noiseCore), exptab);
       v = clampf(l + hp * ng * d.amount[k], 0.0f, d.maxVal);
     }
     out[p * 3 + (2 - k)] = (OUT)(int)v;  // float -> uchar / short by truncation; swizzled to B,G,R
@@ -765,7 +738,7 @@ __global__ __launch_bounds__(256) void k_pipe_finish(const float* __restrict__ t
     float v = t[cp];
     if (!FAST) {
       const float hpC = t[ch] - l[ch];
-      const float ng = 1.0f - expf_glibc_neg(-((hpC * hpC) * d.noiseCore), exptab);
+      const float ng = 1.0f - expf_glibc(-((hpC * hpC) * d.noiseCore), exptab);
       const float hp = t[cp] - l[cp];
       v = fmaxf(fminf(l[cp] + hp * ng * d.amount[cp], d.maxVal), 0.0f);
     }
