@@ -5,7 +5,10 @@
 // reads, feeds and encodes:
 //   * the flags of TestHyperPreview.cpp:40-55 with their names and defaults (image_width / image_height and
 //     enable_pole_removal are defined and never read there: accepted, ignored) and the four glog flags preview.py passes;
-//     additions, opt-in only: --preview_ext jpg|png (png: the same pixels losslessly), --jpeg_threads N (8, at most 16), --device;
+//     additions, opt-in only: --preview_ext jpg|png (png: the same pixels losslessly), --jpeg_threads N (8, at most 16), --device,
+//     --device_jpeg (no value, or =true / =false; S360_PREVIEW_DEVICE_JPEG=1 in the environment switches it on for a caller that
+//     cannot be changed — a flag on the command line, =false included, wins over it, and with --preview_ext png it is ignored): the .jpg files are encoded on the device behind the compose kernel (s360_preview_set_jpeg, quality 95:
+//     the same bytes), the finished file travels to the host instead of the pixels and the pool's threads only write;
 //   * files <binary_prefix>/<i>.bin, i < file_count, with the reference's header checks (magic, file index, file count, sizes
 //     consistent across files; its comparison of the never-initialised timestamps[] is NOT restated); global camera c lives in
 //     file c % file_count; the serial numbers (second 32-bit word of each frame of the first frame set) are sorted AS DECIMAL
@@ -100,6 +103,7 @@ int main(int argc, char** argv) {
       {"frame_count", "0"}, {"rig_json_file", ""}, {"eqr_width", "2048"}, {"eqr_height", "1024"}, {"preview_dest", ""},
       {"gamma", "1.0"}, {"top_cam_index", "0"}, {"bottom_cam_index", "15"}, {"bottom_cam2_index", "16"},
       {"enable_pole_removal", "true"}, {"softmax_coef", "30.0"}, {"preview_ext", "jpg"}, {"jpeg_threads", "8"}, {"device", "0"},
+      {"device_jpeg", ""},
       {"log_dir", ""}, {"stderrthreshold", "0"}, {"v", "0"}, {"logbuflevel", "0"}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -108,6 +112,7 @@ int main(int argc, char** argv) {
     std::string key = a, val;
     const size_t eq = a.find('=');
     if (eq != std::string::npos) { key = a.substr(0, eq); val = a.substr(eq + 1); }
+    else if (key == "device_jpeg") val = "true";
     else { if (i + 1 >= argc) die("flag '" + key + "' is missing its argument"); val = argv[++i]; }
     if (!F.count(key)) { std::fprintf(stderr, "ERROR: unknown command line flag '%s'\n", key.c_str()); return 1; }
     F[key] = val;
@@ -120,6 +125,13 @@ int main(int argc, char** argv) {
   const int jpegThreads = std::max(1, std::min(16, std::atoi(F["jpeg_threads"].c_str())));
   const bool png = F["preview_ext"] == "png";
   if (!png && F["preview_ext"] != "jpg") die("--preview_ext is jpg or png");
+  const char* envJpeg = std::getenv("S360_PREVIEW_DEVICE_JPEG");
+  const bool flagGiven = !F["device_jpeg"].empty();  // a flag on the command line decides; the environment only where there is none
+  const bool flagJpeg = F["device_jpeg"] == "true" || F["device_jpeg"] == "1";
+  if (flagGiven && !flagJpeg && F["device_jpeg"] != "false" && F["device_jpeg"] != "0") die("--device_jpeg is true or false");
+  if (flagJpeg && png) die("--device_jpeg encodes .jpg files: it does not go with --preview_ext png");
+  // (the environment switch is for .jpg output: with --preview_ext png it changes nothing, where the flag is refused)
+  const bool deviceJpeg = flagGiven ? flagJpeg : (!png && envJpeg && envJpeg[0] == '1');
   if (fileCount < 1 || fileCount > 4096) die("--file_count must be at least 1");
   if (startFrame < 0 || frameCountFlag < 0) die("--start_frame and --frame_count must not be negative");
 
@@ -193,8 +205,9 @@ int main(int argc, char** argv) {
                             std::atof(F["softmax_coef"].c_str())) < 0)
       throw std::runtime_error(s360_last_error(nullptr));
     mkdir(F["preview_dest"].c_str(), 0755);
+    if (deviceJpeg && s360_preview_set_jpeg(pv, 1, 95) < 0) throw std::runtime_error(s360_last_error(nullptr));
 
-    const size_t frameBytes = files[0]->frame_size(), outBytes = (size_t)eqrW * eqrH * 3;
+    const size_t frameBytes = files[0]->frame_size(), outBytes = deviceJpeg ? s360_preview_jpeg_bound(pv) : (size_t)eqrW * eqrH * 3;
     uint8_t* in[2][3];
     for (auto& set : in)
       for (auto& p : set)
@@ -225,18 +238,24 @@ int main(int argc, char** argv) {
           freeOut.pop_back();
         }
         const auto f0 = now();  // (waiting for a free output buffer counts as encoding, not as fetching)
-        if (s360_preview_fetch(pv, buf) < 0) throw std::runtime_error(s360_last_error(nullptr));
+        size_t fileBytes = 0;
+        if ((deviceJpeg ? s360_preview_fetch_jpeg(pv, buf, outBytes, &fileBytes) : s360_preview_fetch(pv, buf)) < 0)
+          throw std::runtime_error(s360_last_error(nullptr));
         tFetch += secs(f0, now());
         char name[32];
         std::snprintf(name, sizeof name, "/%06ld.%s", frame, png ? "png" : "jpg");
         const std::string path = F["preview_dest"] + name;
-        pool.add([&, buf, path] {
+        pool.add([&, buf, path, fileBytes] {
           struct Release {
             std::vector<uint8_t*>& v; std::mutex& m; std::condition_variable& c; uint8_t* b;
             ~Release() { { std::lock_guard<std::mutex> lk(m); v.push_back(b); } c.notify_one(); }
           } rel{freeOut, outMu, outCv, buf};
           const auto e0 = std::chrono::steady_clock::now();
-          if (png) pngio::write(path, buf, eqrW, eqrH, 3, 1, 1);
+          if (deviceJpeg) {  // the file is finished: only written
+            pngio::OutFile f(path);
+            f.put(buf, fileBytes);
+            f.close();
+          } else if (png) pngio::write(path, buf, eqrW, eqrH, 3, 1, 1);
           else jpegio::write(path, buf, eqrW, eqrH);
           encodeUs += std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - e0).count();
         });

@@ -501,7 +501,8 @@ inline pngio::Image decode_any(const std::vector<uint8_t>& file, const std::stri
 //     quantisation rounding (jcdctmgr.c: half the divisor added to the magnitude, truncating division);
 //   * the standard Huffman tables of Annex K (jcparam.c), 0xFF bytes stuffed, the last byte padded with 1-bits.
 // tests/test_cpu_preview.py: PIL decodes these files to exactly the pixels it decodes from its own save(quality=95,
-// subsampling=2) of the same image, i.e. the quantised coefficients are equal. Runs on the host: the bitstream is serial.
+// subsampling=2) of the same image, i.e. the quantised coefficients are equal. This writer runs on the host and is the
+// specification of the device's (surround360_amd/csrc/jpeg.hip, include/s360_jpeg.h), which writes the same file byte for byte.
 namespace enc_detail {
 static const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
@@ -601,10 +602,12 @@ struct BitWriter {
   std::vector<uint8_t>& out;
   uint32_t acc = 0;
   int n = 0;
+  size_t nbits = 0;  // bits put so far (flush()'s padding included once it ran)
   explicit BitWriter(std::vector<uint8_t>& o) : out(o) {}
   void put(unsigned code, int len) {
     acc = (acc << len) | (code & ((1u << len) - 1));
     n += len;
+    nbits += (size_t)len;
     while (n >= 8) {
       const uint8_t b = (uint8_t)(acc >> (n - 8));
       out.push_back(b);
@@ -616,21 +619,22 @@ struct BitWriter {
     if (n) put(0x7F, 8 - n);  // the partial byte filled with 1-bits
   }
 };
-}  // namespace enc_detail
-
-// bgr: h rows of w pixels, 3 bytes each (B,G,R), rows contiguous. Returns the file.
-inline std::vector<uint8_t> encode(const uint8_t* bgr, int w, int h, int quality = 95) {
-  using namespace enc_detail;
-  if (w <= 0 || h <= 0 || w > 65535 || h > 65535) throw std::runtime_error("jpeg: image size outside 1..65535");
+// the quantisation tables of a quality (natural order); quality is clamped to 1..100
+inline void quant_tables(int quality, int q[2][64]) {
   if (quality < 1) quality = 1;
   if (quality > 100) quality = 100;
   const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2;  // jpeg_quality_scaling
-  int q[2][64];
   for (int t = 0; t < 2; ++t)
     for (int i = 0; i < 64; ++i) {
       long v = ((long)(t ? kChrQ[i] : kLumQ[i]) * scale + 50L) / 100L;
       q[t][i] = (int)(v <= 0 ? 1 : v > 255 ? 255 : v);  // force_baseline
     }
+}
+
+// The first half of encode(): pixels -> the quantised coefficients of every emitted block, 64 per block in natural order, the
+// blocks in emission order (per MCU Y00 Y01 Y10 Y11 Cb Cr), dummy blocks included. The device encoder's test tap
+// (include/s360_debug_jpeg.h) is compared with this.
+inline std::vector<int16_t> make_blocks(const uint8_t* bgr, int w, int h, const int q[2][64]) {
   // geometry: MCU 16 x 16; Y in whole blocks, chroma in whole blocks of the halved (rounded up) size
   const int mcux = (w + 15) / 16, mcuy = (h + 15) / 16;
   const int ybw = (w + 7) / 8, ybh = (h + 7) / 8;               // Y: blocks that exist
@@ -669,6 +673,92 @@ inline std::vector<uint8_t> encode(const uint8_t* bgr, int w, int h, int quality
       }
     }
   }
+  // one block: samples -> quantised coefficients (natural order)
+  auto make_block = [&](const uint8_t* plane, int stride, int bx, int by, int tq, int* coef) {
+    int d[64];
+    for (int r = 0; r < 8; ++r)
+      for (int c = 0; c < 8; ++c) d[r * 8 + c] = (int)plane[(size_t)(by * 8 + r) * stride + bx * 8 + c] - 128;
+    fdct_islow(d);
+    for (int i = 0; i < 64; ++i) {
+      const int qv = q[tq][i] << 3;
+      int t = d[i];
+      if (t < 0) { t = -t; t += qv >> 1; t = t >= qv ? t / qv : 0; t = -t; }
+      else { t += qv >> 1; t = t >= qv ? t / qv : 0; }
+      coef[i] = t;
+    }
+  };
+  std::vector<int16_t> blocks;
+  blocks.reserve((size_t)mcux * mcuy * 6 * 64);
+  int coef[64], prevDc = 0;
+  for (int my = 0; my < mcuy; ++my)
+    for (int mx = 0; mx < mcux; ++mx) {
+      for (int comp = 0; comp < 3; ++comp) {
+        const int n = comp ? 1 : 2;  // blocks per MCU in each direction
+        const uint8_t* plane = comp == 0 ? Y.data() : comp == 1 ? cbs.data() : crs.data();
+        const int stride = comp ? cW : fW, bwid = comp ? cbw : ybw, bhei = comp ? cbh : ybh;
+        for (int j = 0; j < n; ++j)
+          for (int i = 0; i < n; ++i) {
+            const int bx = mx * n + i, by = my * n + j;
+            if (bx < bwid && by < bhei) {
+              make_block(plane, stride, bx, by, comp ? 1 : 0, coef);
+            } else {  // dummy block (zero AC): the DC of the block before it in the MCU
+              std::memset(coef, 0, sizeof coef);
+              coef[0] = prevDc;
+            }
+            prevDc = coef[0];
+            for (int k = 0; k < 64; ++k) blocks.push_back((int16_t)coef[k]);  // (|coefficient| <= 1024)
+          }
+      }
+    }
+  return blocks;
+}
+
+// The second half: the blocks of make_blocks() as the entropy-coded segment (Huffman codes, extra bits, the last byte padded with
+// 1-bits, 0xFF bytes stuffed), appended to out. bits (may be null): every block's bit length before stuffing.
+inline void emit_blocks(const std::vector<int16_t>& blocks, std::vector<uint8_t>& out, std::vector<uint32_t>* bits) {
+  const EncTable dcT[2] = {EncTable(kDcLumBits, kDcVals), EncTable(kDcChrBits, kDcVals)};
+  const EncTable acT[2] = {EncTable(kAcLumBits, kAcLumVals), EncTable(kAcChrBits, kAcChrVals)};
+  BitWriter bw(out);
+  int lastDc[3] = {0, 0, 0};
+  auto emit_block = [&](const int16_t* coef, int comp) {
+    const int t = comp ? 1 : 0;
+    int diff = coef[0] - lastDc[comp];
+    lastDc[comp] = coef[0];
+    int mag = diff < 0 ? -diff : diff, nb = 0;
+    while (mag) { ++nb; mag >>= 1; }
+    bw.put(dcT[t].code[nb], dcT[t].len[nb]);
+    if (nb) bw.put((unsigned)(diff < 0 ? diff - 1 : diff), nb);
+    int run = 0;
+    for (int k = 1; k < 64; ++k) {
+      const int v = coef[kZigzag[k]];
+      if (!v) { ++run; continue; }
+      while (run > 15) { bw.put(acT[t].code[0xF0], acT[t].len[0xF0]); run -= 16; }
+      int m = v < 0 ? -v : v, n = 0;
+      while (m) { ++n; m >>= 1; }
+      const int sym = (run << 4) | n;
+      bw.put(acT[t].code[sym], acT[t].len[sym]);
+      bw.put((unsigned)(v < 0 ? v - 1 : v), n);
+      run = 0;
+    }
+    if (run) bw.put(acT[t].code[0], acT[t].len[0]);
+  };
+  const size_t n = blocks.size() / 64;
+  for (size_t b = 0; b < n; ++b) {
+    const size_t before = bw.nbits;
+    emit_block(&blocks[b * 64], b % 6 < 4 ? 0 : (int)(b % 6) - 3);
+    if (bits) bits->push_back((uint32_t)(bw.nbits - before));
+  }
+  bw.flush();
+}
+}  // namespace enc_detail
+
+// bgr: h rows of w pixels, 3 bytes each (B,G,R), rows contiguous. Returns the file: the header, then the composition of
+// enc_detail::make_blocks and enc_detail::emit_blocks, then EOI.
+inline std::vector<uint8_t> encode(const uint8_t* bgr, int w, int h, int quality = 95) {
+  using namespace enc_detail;
+  if (w <= 0 || h <= 0 || w > 65535 || h > 65535) throw std::runtime_error("jpeg: image size outside 1..65535");
+  int q[2][64];
+  quant_tables(quality, q);
   std::vector<uint8_t> out;
   out.reserve((size_t)w * h / 2 + 1024);
   auto put16 = [&](int v) { out.push_back((uint8_t)(v >> 8)); out.push_back((uint8_t)v); };
@@ -692,69 +782,7 @@ inline std::vector<uint8_t> encode(const uint8_t* bgr, int w, int h, int quality
   }
   const uint8_t sos[] = {0xFF, 0xDA, 0, 12, 3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0};
   out.insert(out.end(), sos, sos + sizeof sos);
-
-  const EncTable dcT[2] = {EncTable(kDcLumBits, kDcVals), EncTable(kDcChrBits, kDcVals)};
-  const EncTable acT[2] = {EncTable(kAcLumBits, kAcLumVals), EncTable(kAcChrBits, kAcChrVals)};
-  BitWriter bw(out);
-  int lastDc[3] = {0, 0, 0};
-  // one block: samples -> quantised coefficients (natural order). exists == false: a dummy block (zero AC, DC of `prev`)
-  auto make_block = [&](const uint8_t* plane, int stride, int bx, int by, int tq, int* coef) {
-    int d[64];
-    for (int r = 0; r < 8; ++r)
-      for (int c = 0; c < 8; ++c) d[r * 8 + c] = (int)plane[(size_t)(by * 8 + r) * stride + bx * 8 + c] - 128;
-    fdct_islow(d);
-    for (int i = 0; i < 64; ++i) {
-      const int qv = q[tq][i] << 3;
-      int t = d[i];
-      if (t < 0) { t = -t; t += qv >> 1; t = t >= qv ? t / qv : 0; t = -t; }
-      else { t += qv >> 1; t = t >= qv ? t / qv : 0; }
-      coef[i] = t;
-    }
-  };
-  auto emit_block = [&](const int* coef, int comp) {
-    const int t = comp ? 1 : 0;
-    int diff = coef[0] - lastDc[comp];
-    lastDc[comp] = coef[0];
-    int mag = diff < 0 ? -diff : diff, nb = 0;
-    while (mag) { ++nb; mag >>= 1; }
-    bw.put(dcT[t].code[nb], dcT[t].len[nb]);
-    if (nb) bw.put((unsigned)(diff < 0 ? diff - 1 : diff), nb);
-    int run = 0;
-    for (int k = 1; k < 64; ++k) {
-      const int v = coef[kZigzag[k]];
-      if (!v) { ++run; continue; }
-      while (run > 15) { bw.put(acT[t].code[0xF0], acT[t].len[0xF0]); run -= 16; }
-      int m = v < 0 ? -v : v, n = 0;
-      while (m) { ++n; m >>= 1; }
-      const int sym = (run << 4) | n;
-      bw.put(acT[t].code[sym], acT[t].len[sym]);
-      bw.put((unsigned)(v < 0 ? v - 1 : v), n);
-      run = 0;
-    }
-    if (run) bw.put(acT[t].code[0], acT[t].len[0]);
-  };
-  int coef[64], prevDc = 0;
-  for (int my = 0; my < mcuy; ++my)
-    for (int mx = 0; mx < mcux; ++mx) {
-      for (int comp = 0; comp < 3; ++comp) {
-        const int n = comp ? 1 : 2;  // blocks per MCU in each direction
-        const uint8_t* plane = comp == 0 ? Y.data() : comp == 1 ? cbs.data() : crs.data();
-        const int stride = comp ? cW : fW, bwid = comp ? cbw : ybw, bhei = comp ? cbh : ybh;
-        for (int j = 0; j < n; ++j)
-          for (int i = 0; i < n; ++i) {
-            const int bx = mx * n + i, by = my * n + j;
-            if (bx < bwid && by < bhei) {
-              make_block(plane, stride, bx, by, comp ? 1 : 0, coef);
-            } else {  // dummy block: the DC of the block before it in the MCU
-              std::memset(coef, 0, sizeof coef);
-              coef[0] = prevDc;
-            }
-            prevDc = coef[0];
-            emit_block(coef, comp);
-          }
-      }
-    }
-  bw.flush();
+  emit_blocks(make_blocks(bgr, w, h, q), out, nullptr);
   out.push_back(0xFF); out.push_back(0xD9);
   return out;
 }

@@ -44,6 +44,22 @@ int s360_preview_fetch(s360_preview* p, uint8_t* out_bgr);
 /* Device time of the two kernels of the last submitted frame, in ms (hipEvents on the object's stream; waits for that frame). */
 int s360_preview_last_times(s360_preview* p, float* develop_ms, float* compose_ms);
 
+/* The frame as a .jpg file made on the device (include/s360_jpeg.h: the file jpegio::encode / cv::imwrite writes from the same
+ * pixels, byte for byte). on != 0: frames SUBMITTED from now on are also encoded behind the compose kernel, on the same stream,
+ * into a buffer of their slot; quality as libjpeg's, clamped to 1..100 (the reference's files: 95). Changing the quality waits
+ * for the frames in flight; frames already submitted keep the quality they were submitted with, header and scan. on == 0: frames submitted from now on are not encoded. An equirect beyond the encoder's limits:
+ * S360_ERR_INVALID_ARG. s360_preview_fetch keeps working on encoded frames (it takes the pixels). */
+int s360_preview_set_jpeg(s360_preview* p, int on, int quality);
+/* A size no .jpg of the object's equirect exceeds: the buffer s360_preview_fetch_jpeg wants (0 beyond the encoder's limits). */
+size_t s360_preview_jpeg_bound(const s360_preview* p);
+/* As s360_preview_fetch, but takes the OLDEST unfetched frame as its file: the byte count travels first, then exactly that many
+ * bytes (out in page-locked memory makes that one direct transfer). *n_out: the file's size. S360_ERR_STATE when that frame was
+ * submitted with the encoder off — it stays queued for s360_preview_fetch; S360_ERR_INVALID_ARG when cap is smaller than the file
+ * (*n_out = the size needed; the frame stays queued). */
+int s360_preview_fetch_jpeg(s360_preview* p, uint8_t* out, size_t cap, size_t* n_out);
+/* Device time of the encoder's kernels for the last frame submitted with the encoder on, in ms (waits for that frame). */
+int s360_preview_last_jpeg_time(s360_preview* p, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

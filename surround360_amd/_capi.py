@@ -123,10 +123,15 @@ DEBUG_FLOW_PYRAMID_SYMBOLS = ["s360_debug_flow_prepare", "s360_debug_resize_line
 DEBUG_CUBEMAP_SYMBOLS = ["s360_debug_cubemap_tiles", "s360_debug_cubemap"]
 # ... and the ones include/s360_preview.h declares (a header of its own: pole-camera previews from packed capture frames)
 PREVIEW_SYMBOLS = ["s360_preview_create", "s360_preview_destroy", "s360_preview_cameras", "s360_preview_render_packed",
-                   "s360_preview_submit_packed", "s360_preview_fetch", "s360_preview_last_times"]
+                   "s360_preview_submit_packed", "s360_preview_fetch", "s360_preview_last_times",
+                   "s360_preview_set_jpeg", "s360_preview_jpeg_bound", "s360_preview_fetch_jpeg", "s360_preview_last_jpeg_time"]
 # ... and its test taps, include/s360_debug_preview.h
 DEBUG_PREVIEW_SYMBOLS = ["s360_debug_preview_camera", "s360_debug_preview_map", "s360_debug_preview_set_maps",
                          "s360_debug_preview_developed", "s360_debug_preview_remapped"]
+# ... and the ones include/s360_jpeg.h declares (a header of its own: baseline JPEG files encoded on the device)
+JPEG_SYMBOLS = ["s360_jpeg_create", "s360_jpeg_destroy", "s360_jpeg_bound", "s360_jpeg_encode", "s360_jpeg_last_time"]
+# ... and its test tap, include/s360_debug_jpeg.h
+DEBUG_JPEG_SYMBOLS = ["s360_debug_jpeg_blocks"]
 
 
 class FlowPrepareOut(C.Structure):
@@ -247,6 +252,26 @@ def lib():
         L.s360_debug_preview_set_maps.argtypes = [C.c_void_p] * 4
         L.s360_debug_preview_developed.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.s360_debug_preview_remapped.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.s360_preview_set_jpeg.restype = C.c_int
+        L.s360_preview_set_jpeg.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.s360_preview_jpeg_bound.restype = C.c_size_t
+        L.s360_preview_jpeg_bound.argtypes = [C.c_void_p]
+        L.s360_preview_fetch_jpeg.restype = C.c_int
+        L.s360_preview_fetch_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.s360_preview_last_jpeg_time.restype = C.c_int
+        L.s360_preview_last_jpeg_time.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.s360_jpeg_create.restype = C.c_int
+        L.s360_jpeg_create.argtypes = [C.POINTER(C.c_void_p)] + [C.c_int] * 4
+        L.s360_jpeg_destroy.restype = None
+        L.s360_jpeg_destroy.argtypes = [C.c_void_p]
+        L.s360_jpeg_bound.restype = C.c_size_t
+        L.s360_jpeg_bound.argtypes = [C.c_int, C.c_int]
+        L.s360_jpeg_encode.restype = C.c_int
+        L.s360_jpeg_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.s360_jpeg_last_time.restype = C.c_int
+        L.s360_jpeg_last_time.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.s360_debug_jpeg_blocks.restype = C.c_int
+        L.s360_debug_jpeg_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.s360_isp_config_defaults.restype = None
         L.s360_isp_destroy.restype = None
         L.s360_isp_destroy.argtypes = [C.c_void_p]

@@ -12,16 +12,21 @@
 // All three are per-pixel stream / gather kernels bound by memory traffic; the float4 intermediate between develop and compose
 // (16 bytes per half-resolution pixel and layer) stays in HBM. float arithmetic in the reference's operation order (the library
 // is built with -ffp-contract=off).
+//
+// s360_preview_set_jpeg: the frame is also encoded as a baseline JPEG file behind k_preview_compose, on the same stream
+// (jpeg.hip; the per-slot scan buffer travels to the host instead of the pixels).
 #include "../../include/s360_debug_preview.h"
 #include "../../include/s360_preview.h"
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "core.hpp"
 #include "devmath.hpp"
 #include "expf_glibc.hpp"
+#include "jpeg.hpp"
 #include "render_kernels.hpp"
 
 namespace s360 {
@@ -281,6 +286,13 @@ struct s360_preview {
   DevBuf dMap[3], dPacked[3], dDev[3], dOut[2], dTab, dExp, dTapOut, dTapRemap;
   hipEvent_t evDone[2] = {nullptr, nullptr}, evT[3] = {nullptr, nullptr, nullptr};
   unsigned long long submitted = 0, fetched = 0;
+  // .jpg output (s360_preview_set_jpeg): the encoder, the scan and its byte count per slot
+  std::unique_ptr<JpegEncoder> jenc;
+  bool jpegOn = false, slotJpeg[2] = {false, false}, jpegTimed = false;
+  DevBuf dScan[2], dCount[2];
+  hipEvent_t evJ[2] = {nullptr, nullptr};
+  uint32_t* hCount = nullptr;
+  uint8_t slotHeader[2][JPEG_HEADER_BYTES];  // written at submit: the tables of the encoder that made the slot's scan
   size_t packed_bytes(int bits) const { return bits == 8 ? (size_t)rawW * rawH : (size_t)rawH * (3 * (size_t)rawW / 2); }
   ~s360_preview() {
     if (st) (void)hipStreamSynchronize(st);
@@ -289,6 +301,9 @@ struct s360_preview {
       if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : evT)
       if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : evJ)
+      if (e) (void)hipEventDestroy(e);
+    if (hCount) (void)hipHostFree(hCount);
     if (st) (void)hipStreamDestroy(st);
     if (stCopy) (void)hipStreamDestroy(stCopy);
   }
@@ -422,8 +437,60 @@ void submit(s360_preview* p, const uint8_t* const frames[3], int bits) {
   compose(p, p->dOut[slot].as<unsigned char>(), nullptr, -1);
   S360_HIP(hipEventRecord(p->evT[2], p->st));
   S360_HIP(hipGetLastError());
+  p->slotJpeg[slot] = p->jpegOn;
+  if (p->jpegOn) {
+    S360_HIP(hipEventRecord(p->evJ[0], p->st));
+    p->jenc->encode(p->dOut[slot].as<uint8_t>(), p->W, p->H, p->dScan[slot].as<uint8_t>(), p->dScan[slot].cap, p->dCount[slot].as<uint32_t>(),
+                    p->st);
+    S360_HIP(hipEventRecord(p->evJ[1], p->st));
+    p->jenc->header(p->slotHeader[slot], p->W, p->H);
+    p->jpegTimed = true;
+  }
   S360_HIP(hipEventRecord(p->evDone[slot], p->st));
   p->submitted += 1;
+}
+void set_jpeg(s360_preview* p, int on, int quality) {
+  if (!on) {
+    p->jpegOn = false;
+    return;
+  }
+  need(jpeg_size_ok(p->W, p->H), "s360_preview_set_jpeg: the equirect is larger than the JPEG encoder's limits (include/s360_jpeg.h)");
+  S360_HIP(hipSetDevice(p->device));
+  const int q = quality < 1 ? 1 : quality > 100 ? 100 : quality;
+  if (!p->jenc || p->jenc->quality != q) {
+    S360_HIP(hipStreamSynchronize(p->st));  // (frames in flight may still use the tables of the encoder that goes)
+    std::unique_ptr<JpegEncoder> e(new JpegEncoder);
+    e->init(p->W, p->H, q, p->st);
+    p->jenc = std::move(e);
+  }
+  for (int k = 0; k < 2; ++k) {
+    p->dScan[k].ensure(jpeg_scan_cap(p->W, p->H));
+    p->dCount[k].ensure(sizeof(uint32_t));
+    if (!p->evJ[k]) S360_HIP(hipEventCreate(&p->evJ[k]));
+  }
+  if (!p->hCount) S360_HIP(hipHostMalloc((void**)&p->hCount, sizeof(uint32_t), hipHostMallocDefault));
+  p->jpegOn = true;
+}
+void fetch_jpeg(s360_preview* p, uint8_t* out, size_t cap, size_t* n_out) {
+  *n_out = 0;
+  if (p->fetched == p->submitted) throw Error(S360_ERR_STATE, "s360_preview_fetch_jpeg: no submitted frame is waiting");
+  const int slot = (int)(p->fetched & 1);
+  if (!p->slotJpeg[slot]) throw Error(S360_ERR_STATE, "s360_preview_fetch_jpeg: the oldest frame was submitted with the encoder off (s360_preview_fetch takes it)");
+  S360_HIP(hipSetDevice(p->device));
+  // the byte count first, then exactly that many bytes
+  S360_HIP(hipStreamWaitEvent(p->stCopy, p->evDone[slot], 0));
+  S360_HIP(hipMemcpyAsync(p->hCount, p->dCount[slot].p, sizeof(uint32_t), hipMemcpyDeviceToHost, p->stCopy));
+  S360_HIP(hipStreamSynchronize(p->stCopy));
+  const size_t n = *p->hCount;
+  if (n > p->dScan[slot].cap) throw Error(S360_ERR_STATE, "s360_preview_fetch_jpeg: the scan is longer than its worst case");
+  *n_out = JPEG_HEADER_BYTES + n + 2;
+  need(out && cap >= *n_out, "s360_preview_fetch_jpeg: cap is smaller than the file (its size is in *n_out; the frame stays queued)");
+  p->fetched += 1;  // (a failed transfer does not leave the frame in the queue)
+  std::memcpy(out, p->slotHeader[slot], JPEG_HEADER_BYTES);  // (the encoder may have been replaced by another quality since)
+  S360_HIP(hipMemcpyAsync(out + JPEG_HEADER_BYTES, p->dScan[slot].p, n, hipMemcpyDeviceToHost, p->stCopy));
+  S360_HIP(hipStreamSynchronize(p->stCopy));
+  out[JPEG_HEADER_BYTES + n] = 0xFF;
+  out[JPEG_HEADER_BYTES + n + 1] = 0xD9;
 }
 void fetch(s360_preview* p, uint8_t* out) {
   if (p->fetched == p->submitted) throw Error(S360_ERR_STATE, "s360_preview_fetch: no submitted frame is waiting");
@@ -497,6 +564,27 @@ int s360_preview_last_times(s360_preview* p, float* develop_ms, float* compose_m
     S360_HIP(hipEventSynchronize(p->evT[2]));
     S360_HIP(hipEventElapsedTime(develop_ms, p->evT[0], p->evT[1]));
     S360_HIP(hipEventElapsedTime(compose_ms, p->evT[1], p->evT[2]));
+  });
+}
+int s360_preview_set_jpeg(s360_preview* p, int on, int quality) {
+  return guard([&] {
+    need(p != nullptr, "null argument");
+    set_jpeg(p, on, quality);
+  });
+}
+size_t s360_preview_jpeg_bound(const s360_preview* p) { return p && jpeg_size_ok(p->W, p->H) ? jpeg_file_bound(p->W, p->H) : 0; }
+int s360_preview_fetch_jpeg(s360_preview* p, uint8_t* out, size_t cap, size_t* n_out) {
+  return guard([&] {
+    need(p && n_out, "null argument");
+    fetch_jpeg(p, out, cap, n_out);
+  });
+}
+int s360_preview_last_jpeg_time(s360_preview* p, float* ms) {
+  return guard([&] {
+    need(p && ms, "null argument");
+    if (!p->jpegTimed) throw Error(S360_ERR_STATE, "s360_preview_last_jpeg_time: no frame was submitted with the encoder on");
+    S360_HIP(hipEventSynchronize(p->evJ[1]));
+    S360_HIP(hipEventElapsedTime(ms, p->evJ[0], p->evJ[1]));
   });
 }
 

@@ -79,6 +79,33 @@ class Preview:
         check(lib().s360_preview_last_times(self.h, C.byref(d), C.byref(c)))
         return d.value, c.value
 
+    # ---- the frame as a .jpg file encoded on the device (include/s360_jpeg.h) ----
+    def set_jpeg(self, on, quality=95):
+        """Frames submitted from now on are also (on) / no longer (off) encoded behind the compose kernel."""
+        check(lib().s360_preview_set_jpeg(self.h, 1 if on else 0, int(quality)))
+
+    def jpeg_bound(self):
+        return int(lib().s360_preview_jpeg_bound(self.h))
+
+    def fetch_jpeg(self, cap=None):
+        """The oldest submitted frame that was not fetched yet, as the bytes of its .jpg file."""
+        if getattr(self, "_jpeg_out", None) is None:
+            self._jpeg_out = np.empty(self.jpeg_bound(), np.uint8)
+        n = C.c_size_t(0)
+        check(lib().s360_preview_fetch_jpeg(self.h, _p(self._jpeg_out), self._jpeg_out.size if cap is None else int(cap), C.byref(n)))
+        return self._jpeg_out[:n.value].tobytes()
+
+    def render_packed_jpeg(self, top, bottom, bottom2, bits):
+        """render_packed with the file instead of the pixels (the encoder must be on)."""
+        self.submit_packed(top, bottom, bottom2, bits)
+        return self.fetch_jpeg()
+
+    def last_jpeg_time(self):
+        """Device time of the encoder's kernels for the last frame submitted with the encoder on, ms."""
+        ms = C.c_float(0)
+        check(lib().s360_preview_last_jpeg_time(self.h, C.byref(ms)))
+        return ms.value
+
     # ---- test taps (include/s360_debug_preview.h); layer: 0 top, 1 bottom, 2 secondary bottom ----
     def debug_camera(self, layer):
         c = Camera()

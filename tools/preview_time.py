@@ -7,7 +7,11 @@ tests/golden/rig_17cam.json: device ms of k_preview_develop (three layers) and k
 frames and every camera's serial number are written; the program reads nothing else): frames per second, and with
 S360_PREVIEW_TIMES=1 where the wall time went — reading, enqueueing, waiting for the device, JPEG encoding + writing on the
 encoder threads.
-usage: python tools/preview_time.py [--reps 30] [--frames 48] [--rounds 3] [--out profiles/preview.txt]"""
+(3) --device_jpeg (profiles/preview_jpeg.txt): the JPEG encoder on the device (include/s360_jpeg.h behind the compose kernel,
+s360_preview_set_jpeg) — its device time per frame from the object's HIP events (s360_preview_last_jpeg_time), median of `--reps`
+warm frames, next to (1); and the program of (2) with --device_jpeg off and on ALTERNATING within every round of one call, for
+--jpeg_threads 8, 16 and 1: the same binary with the switch off is the baseline.
+usage: python tools/preview_time.py [--device_jpeg] [--reps 30] [--frames 48] [--rounds 3] [--out profiles/preview.txt]"""
 import argparse
 import os
 import re
@@ -28,9 +32,12 @@ ap.add_argument("--frames", type=int, default=48)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--size", type=int, default=2048)
 ap.add_argument("--program", default=os.path.join(ROOT, "host", "TestHyperPreview"))
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "preview.txt"))
+ap.add_argument("--out", default=None)
+ap.add_argument("--device_jpeg", action="store_true")
 ap.add_argument("--timeout", type=int, default=240)
 args = ap.parse_args()
+if args.out is None:
+    args.out = os.path.join(ROOT, "profiles", "preview_jpeg.txt" if args.device_jpeg else "preview.txt")
 RIG = os.path.join(ROOT, "tests", "golden", "rig_17cam.json")
 lines = []
 
@@ -75,6 +82,15 @@ def kernels():
         say("%-30s median %.4f ms  min %.4f  max %.4f  (%d frames; compulsory traffic %.1f MB = %.0f GB/s at the median)" %
             (name, med, min(t), max(t), len(t), nbytes / 1e6, nbytes / 1e6 / med if med > 0 else 0.0))
     say("  (compulsory traffic: every input and output byte once; compose's 16 taps per layer and pixel mostly hit in cache)")
+    if args.device_jpeg:
+        pv.set_jpeg(True, 95)
+        enc, size = [], 0
+        for k in range(5 + args.reps):
+            size = len(pv.render_packed_jpeg(*frames[k & 1], 12))
+            if k >= 5:
+                enc.append(pv.last_jpeg_time())
+        say("%-30s median %.4f ms  min %.4f  max %.4f  (%d frames, quality 95, a file of %.2f MB; the host writer needs about 33 ms of one thread per frame: profiles/preview.txt)" %
+            ("JPEG encoder (11 kernels)", float(np.median(enc)), min(enc), max(enc), len(enc), size / 1e6))
     pv.close()
 
 
@@ -105,10 +121,11 @@ def program():
     try:
         capture(tmp, args.frames)
         for r in range(args.rounds):
-            for threads in (8, 16, 1):
-                dest = os.path.join(tmp, "out_%d_%d" % (r, threads))
+            for threads, on in [(t, o) for t in (8, 16, 1) for o in ((False, True) if args.device_jpeg else (False,))]:
+                dest = os.path.join(tmp, "out_%d_%d_%d" % (r, threads, on))
                 t0 = time.time()
-                p = subprocess.run([args.program, "--rig_json_file", RIG, "--binary_prefix", tmp, "--preview_dest", dest, "--jpeg_threads", str(threads)],
+                p = subprocess.run([args.program, "--rig_json_file", RIG, "--binary_prefix", tmp, "--preview_dest", dest, "--jpeg_threads", str(threads)] +
+                                   (["--device_jpeg"] if on else []),
                                    capture_output=True, text=True, timeout=args.timeout, env=dict(os.environ, S360_PREVIEW_TIMES="1"))
                 wall = time.time() - t0
                 if p.returncode != 0:
@@ -116,7 +133,9 @@ def program():
                     return
                 m = re.search(r"preview times: (.*)", p.stderr)
                 size = sum(os.path.getsize(os.path.join(dest, f)) for f in os.listdir(dest))
-                say("round %d, --jpeg_threads %2d: process %.2f s; %s; %d files, %.1f MB" % (r, threads, wall, m.group(1) if m else "?", len(os.listdir(dest)), size / 1e6))
+                say("round %d, --jpeg_threads %2d%s: process %.2f s; %s; %d files, %.1f MB" %
+                    (r, threads, (", --device_jpeg" if on else ", host encoder") if args.device_jpeg else "", wall, m.group(1) if m else "?",
+                     len(os.listdir(dest)), size / 1e6))
                 shutil.rmtree(dest)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
@@ -126,5 +145,8 @@ say("preview: %d x %d raw, 12 bits packed, equirect 2048 x 1024, gamma 1, softma
 kernels()
 say("host/TestHyperPreview, %d frame sets of 17 cameras in two .bin files (page cache warm after the first round), .jpg output" % args.frames)
 program()
+if args.device_jpeg:
+    say("(with --device_jpeg 'encoding + writing' is writing alone: the pool's threads receive finished files. The windows are short, "
+        "0.1 - 1.6 s for %d frames; 'process' includes start-up, the page-locked buffers and the maps)" % args.frames)
 os.makedirs(os.path.dirname(args.out), exist_ok=True)
 open(args.out, "w").write("\n".join(lines) + "\n")
