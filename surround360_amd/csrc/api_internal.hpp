@@ -1,0 +1,42 @@
+// api_internal.hpp — the few helpers that the files of the C ABI share (api.hip, api_ops.hip, api_png.hip, api_taps.hip,
+// api_isp.hip), besides the guard (api_guard.hpp).
+#pragma once
+#include <string>
+
+#include "api_guard.hpp"
+#include "ctx.hpp"
+#include "render.hpp"
+
+namespace s360 {
+
+// api.hip: throws S360_ERR_HIP when a banded sweep of one of the context's flow engines timed out (and resets their error words).
+// `frame_words` (a fetch of a finished frame): the three sweep error words that frame snapshotted in front of its outDone event
+// (render.hpp); only a non-zero snapshot looks at the engines.
+void check_sweep_error(s360_ctx* c, const unsigned* frame_words = nullptr);
+// api.hip: where the named 8-bit intermediate of a slot's latest frame lies on the device (the names of s360_frame_get_u8)
+const void* frame_u8_source(s360_ctx* c, FrameState& F, const std::string& n, int idx, bool pack_eye, int& w, int& h, int& ch);
+// api.hip: previous state handed in for one pair: its place j in the block the state is laid out for (render.hpp PrevLayout) ...
+PrevLayout prev_side_block(s360_ctx* c, FrameState& F, int pair, int& j);
+// ... and the book-keeping of state that arrives in halves (s360_frame_set_prev_images_png / s360_frame_set_prev_flow)
+void prev_side_arrived(FrameState& F, int pair, unsigned bits);
+void prev_pole_arrived(s360_ctx* c, FrameState& F, int unit, unsigned bits);
+void prev_pr_arrived(FrameState& F, unsigned bits);
+// api_png.hip: host threads for a PNG file's CRCs (developer switch S360_PNG_CRC_THREADS)
+int png_crc_threads();
+
+inline void h2d(s360_ctx* c, void* d, const void* h, size_t n) {
+  S360_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, c->st));
+}
+// Frame pipelining: frame_finish runs on st2. Anything enqueued on st that READS what frame_finish writes (panoramas,
+// warped poles, extended pole images, the stacked equirect) must be ordered after it: the host waits for st2 first.
+inline void wait_finish_stream(s360_ctx* c) {
+  if (c->st2) S360_HIP(hipStreamSynchronize(c->st2));
+}
+inline void d2h(s360_ctx* c, void* h, const void* d, size_t n) {
+  if (c->st2) S360_HIP(hipStreamSynchronize(c->st2));  // frame pipelining: the data may come from the finish stream
+  S360_HIP(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, c->st));
+  S360_HIP(hipStreamSynchronize(c->st));
+  check_sweep_error(c);
+}
+
+}  // namespace s360

@@ -44,6 +44,28 @@ struct DevBuf {
   template <typename T>
   T* as() const { return reinterpret_cast<T*>(p); }
 };
+// ... and its twin in page-locked host memory: the landing areas of small device -> host copies (band tables, error words)
+struct PinBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  PinBuf() {}
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { release(); }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  void ensure(size_t bytes) {
+    if (bytes <= cap) return;
+    release();
+    S360_HIP(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+    cap = bytes;
+  }
+  template <typename T>
+  T* as() const { return reinterpret_cast<T*>(p); }
+};
 
 // Per-kernel-family device timing with HIP events on the stream the kernels run on.
 struct Profiler {
@@ -106,7 +128,7 @@ struct ProfScope {
   ~ProfScope() { p.end(h); }
 };
 
-// api.hip: is the context with this uid (s360_ctx::uid, unique per process) still alive?
+// api.hip (the context registry): is the context with this uid (s360_ctx::uid, unique per process) still alive?
 bool context_alive(unsigned long long uid);
 
 }  // namespace s360

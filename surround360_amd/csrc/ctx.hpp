@@ -17,7 +17,7 @@ struct SlotScratch;  // render.hpp: buffers shared by the frame slots of a conte
 }
 
 struct s360_ctx {
-  // Every C-ABI entry point that takes a context holds this lock for its whole duration (api.hip `guard`): a context is
+  // Every C-ABI entry point that takes a context holds this lock for its whole duration (api_guard.hpp `guard`): a context is
   // safe to call from any number of host threads — the 14 std::threads of TRSP:320-335 may share one — and the calls
   // execute one after the other in lock order. Recursive: batch entry points call the single-pair ones.
   mutable std::recursive_mutex mu;
@@ -42,10 +42,9 @@ struct s360_ctx {
   hipStream_t stUp = nullptr;
   hipStream_t stDown = nullptr;  // s360_frame_download_equirect_of: device -> host copy of a finished frame
   hipEvent_t evDown = nullptr;   // ... and what its host thread sleeps on with the context lock released
-  unsigned* downErr = nullptr;   // ... and that frame's sweep error words (pinned; copied on stDown with the pixels)
+  s360::PinBuf downErr;          // ... and that frame's sweep error words (copied on stDown with the pixels)
   bool png_encode = false;       // s360_set_png_encode: every finished frame is also encoded as a PNG on the device
-  void* pngMetaHost = nullptr;   // pinned landing area of a frame's band table (s360_frame_download_png)
-  size_t pngMetaHostBytes = 0;
+  s360::PinBuf pngMetaHost;      // landing area of a frame's band table (s360_frame_download_png)
   // A batch of PNG files encoded by one launch sequence (png_batch_enqueue): the state images of a frame
   // (s360_frame_encode_state_pngs -> statePng) and the operator form (s360_encode_png_batch -> opPng). Buffers are allocated on
   // first use, grow only, and belong to the context. `gen` counts the encode calls: a fetch that finds another batch after its
@@ -53,10 +52,8 @@ struct s360_ctx {
   struct PngBatch {
     s360::PngBatchPlan plan;
     s360::DevBuf table, scratch, meta, files;
-    void* tabHost = nullptr;   // pinned: the table as it is uploaded
-    size_t tabHostBytes = 0;
-    void* metaHost = nullptr;  // pinned: the band tables of all images, copied behind the gather
-    size_t metaHostBytes = 0;
+    s360::PinBuf tabHost;   // the table as it is uploaded
+    s360::PinBuf metaHost;  // the band tables of all images, copied behind the gather
     hipEvent_t evEnc = nullptr, evRead = nullptr;  // behind the band tables' copy / behind the latest fetch's copy
     hipEvent_t evAfter = nullptr;                  // frame pipelining: orders the encode behind the finish stream
     bool haveEnc = false, haveRead = false, events = false;

@@ -612,7 +612,6 @@ void isp_release(s360_isp* o) {
                  o->timedMs / (double)o->timedImages);
   if (o->evT0) { (void)hipEventDestroy(o->evT0); (void)hipEventDestroy(o->evT1); o->evT0 = o->evT1 = nullptr; }
   if (o->hStuckCount) { (void)hipHostFree(o->hStuckCount); o->hStuckCount = nullptr; }
-  if (o->hPngMeta) { (void)hipHostFree(o->hPngMeta); o->hPngMeta = nullptr; o->hPngMetaBytes = 0; }
   if (o->st) {
     (void)hipSetDevice(o->device);
     (void)hipStreamSynchronize(o->st);

@@ -79,8 +79,7 @@ struct s360_isp {
   // s360_isp_process_png / _packed_png (include/s360_isp_png.h): the PNG encoder's band scratch, band table and file image, and the
   // band table's page-locked landing place. Allocated on first use, grow only.
   s360::DevBuf dPngScratch, dPngMeta, dPngFile;
-  void* hPngMeta = nullptr;
-  size_t hPngMetaBytes = 0;
+  s360::PinBuf hPngMeta;
   // S360_ISP_TIMES=1 (developer switch, tools/unpack_time.py): HIP events around an image's kernels on this object's stream; the sum
   // is printed to stderr when the object is destroyed
   hipEvent_t evT0 = nullptr, evT1 = nullptr;

@@ -25,12 +25,10 @@
 
 #include "../../include/s360_debug_jpeg.h"
 #include "../../include/s360_jpeg.h"
+#include "api_guard.hpp"
 #include "devmath.hpp"
 
 namespace s360 {
-
-void set_thread_error(const std::string& m);  // api.hip
-
 namespace {
 
 // ---- the standard tables (ITU-T T.81 Annex K, as jcparam.c holds them) ------------------------------------------------
@@ -528,23 +526,6 @@ struct s360_jpeg {
 };
 
 namespace {
-
-template <typename F>
-int guard(F&& f) {
-  try {
-    f();
-    return S360_OK;
-  } catch (const Error& e) {
-    set_thread_error(e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_thread_error(e.what());
-    return S360_ERR_STATE;
-  }
-}
-void need(bool ok, const char* what) {
-  if (!ok) throw Error(S360_ERR_INVALID_ARG, what);
-}
 
 void jpeg_init(s360_jpeg* e, int device, int max_w, int max_h, int quality) {
   need(jpeg_size_ok(max_w, max_h), "s360_jpeg_create: size outside 1..65535 or more than 431 220 MCUs of 16 x 16 pixels");

@@ -23,6 +23,7 @@
 #include <memory>
 #include <vector>
 
+#include "api_guard.hpp"
 #include "core.hpp"
 #include "devmath.hpp"
 #include "expf_glibc.hpp"
@@ -30,9 +31,6 @@
 #include "render_kernels.hpp"
 
 namespace s360 {
-
-void set_thread_error(const std::string& m);  // api.hip: what s360_last_error(NULL) returns on this thread
-
 namespace {
 
 struct PreviewCam {
@@ -237,9 +235,6 @@ __global__ __launch_bounds__(PC_W* PC_H) void k_preview_compose(ComposeArgs a, i
 }
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-void need(bool ok, const char* what) {
-  if (!ok) throw Error(S360_ERR_INVALID_ARG, what);
-}
 
 // Camera::createRescaledCamera (Camera.cpp:273-289): int() of the scaled resolution, FLOAT scale factors applied to the double
 // principal point and focal length
@@ -310,20 +305,6 @@ struct s360_preview {
 };
 
 namespace {
-
-template <typename F>
-int guard(F&& f) {
-  try {
-    f();
-    return S360_OK;
-  } catch (const Error& e) {
-    set_thread_error(e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    set_thread_error(e.what());
-    return S360_ERR_STATE;
-  }
-}
 
 void develop(s360_preview* p, const bool changed[3], int bits) {
   DevelopArgs a;

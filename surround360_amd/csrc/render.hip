@@ -449,7 +449,7 @@ static void dev_pole_removal(s360_ctx* c, FrameState& F, bool use_prev) {
   }
   F.have_prev_pr = true;
   F.last_pr = cur;
-  F.prevPrGot = 0;  // (halves of a hand-over in two calls do not outlive a rendered frame: api.hip)
+  F.prevPrGot = 0;  // (halves of a hand-over in two calls do not outlive a rendered frame: api_png.hip, api.hip)
 }
 
 static void ensure_maps(s360_ctx* c) {
@@ -523,8 +523,9 @@ static void side_stage(s360_ctx* c, const std::vector<int>& slotIds, int p0, int
   hipStream_t st = c->st;
   const int camW = g.cam_image_width, camH = g.cam_image_height, ow = g.overlap_image_width;
   const int stripW = c->P.eqr_width / P;
-  const size_t pn = (size_t)camW * camH, on = (size_t)ow * camH;
-  const int n = p1 - p0;
+  const PrevLayout L(c, p0, p1);
+  const size_t pn = (size_t)camW * camH, on = L.on;
+  const int n = L.n;
   std::vector<FrameState*> Fs;
   for (int k : slotIds) {
     SlotScope ss(c, k);
@@ -576,8 +577,8 @@ static void side_stage(s360_ctx* c, const std::vector<int>& slotIds, int p0, int
       }
     }
     const int cur = F.cur_side;
-    F.overlaps[cur].ensure(2 * n * on * sizeof(uchar4));
-    F.sideFlows.ensure(2 * n * on * sizeof(float2));
+    F.overlaps[cur].ensure(L.overlaps_bytes());
+    F.sideFlows.ensure(L.side_flows_bytes());
     {
       ProfScope ps(prof, "crop_overlaps");
       launch_crop_overlaps(st, F.sc->proj.as<uchar4>(), camW, camH, P, ow, F.overlaps[cur].as<uchar4>(), p0, p1);
@@ -607,9 +608,9 @@ static void side_stage(s360_ctx* c, const std::vector<int>& slotIds, int p0, int
         float2* out = F.sideFlows.as<float2>();
         const float2* pf = usePrev ? F.sideFlows.as<float2>() : nullptr;  // (in place: read at the flow's entry, written at its end)
         if (ltor)
-          for (int j = 0; j < n; ++j) fb.add_flow(base + j, base + n + j, out + on * j, pf ? pf + on * j : nullptr);
+          for (int j = 0; j < n; ++j) fb.add_flow(base + j, base + n + j, out + L.left(j), pf ? pf + L.left(j) : nullptr);
         if (rtol)
-          for (int j = 0; j < n; ++j) fb.add_flow(base + n + j, base + j, out + on * (n + j), pf ? pf + on * (n + j) : nullptr);
+          for (int j = 0; j < n; ++j) fb.add_flow(base + n + j, base + j, out + L.right(j), pf ? pf + L.right(j) : nullptr);
       }
       return fb;
     };
@@ -678,7 +679,7 @@ void dev_pole_unit_post(s360_ctx* c, const uchar4* extFisheye, const float2* flo
   FrameState& F = frame_state(c);
   PoleWarpParams pw;
   pw.cols = cols; pw.rows = rows; pw.extW = extW;
-  pw.maxBlendX = int(float(cols) * (1.2f - 1.0f));  // TRSP:507 (kExtendFrac - 1.0f)
+  pw.maxBlendX = int(float(cols) * (kExtendFrac - 1.0f));  // TRSP:507 (kExtendFrac - 1.0f)
   pw.poleCameraRadius = c->ramp.poleCameraRadius;
   pw.phiRampStart = c->ramp.phiRampStart;
   pw.phiMid = c->ramp.phiMid;
@@ -731,10 +732,8 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
   const size_t en = (size_t)W * H;
   if (!c->P.enable_top) { pole_mask &= ~3; composite_mask &= ~3; }
   if (!c->P.enable_bottom) { pole_mask &= ~12; composite_mask &= ~12; }
-  const int rowsT = g.top_rows, rowsB = g.bottom_rows;
-  const int extW = int(float(W) * 1.2f);  // TRSP:400-401
-  const size_t xs = (size_t)extW * std::max(rowsT, rowsB);  // slot stride of the extended images / pole flows
-  auto rowsOf = [&](int u) { return u < 2 ? rowsT : rowsB; };
+  const PrevLayout L(c);
+  const int rowsT = L.rowsT, rowsB = L.rowsB, extW = L.extW;
   if (pole_mask) ensure_maps(c);
   bool usePrev = use_prev != 0 && pole_mask != 0;
   for (int k : slotIds) {
@@ -772,8 +771,8 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
     if (!pole_mask) continue;
     // ---- pole units (TRSP:811-860): 0 top_left, 1 top_right, 2 bottom_left, 3 bottom_right ----
     const int cur = F.cur_pole;
-    F.extImgs[cur].ensure(6 * xs * sizeof(uchar4));
-    F.poleFlows.ensure(4 * xs * sizeof(float2));
+    F.extImgs[cur].ensure(L.ext_bytes());
+    F.poleFlows.ensure(L.pole_flows_bytes());
     uchar4* ext = F.extImgs[cur].as<uchar4>();
     wait_for_uploads(c, st);
     {
@@ -786,7 +785,7 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
         launch_remap_cubic_u8c4_packed(st, F.topSrc.as<uchar4>(), F.topW, F.topH, c->topMap.as<float2>(),
                                        pk.packed.as<unsigned>(), pk.tiles.p, F.sc->topSph.as<uchar4>(), W, rowsT,
                                        F.tab.dev, 1, yfs, c->P.std_alpha_feather_size);
-        launch_extend_wrap(st, F.sc->topSph.as<uchar4>(), nullptr, W, rowsT, ext + 4 * xs, extW);
+        launch_extend_wrap(st, F.sc->topSph.as<uchar4>(), nullptr, W, rowsT, ext + L.fisheye(0), extW);
       }
       if (pole_mask & 12) {
         if (!F.have_bottom) throw Error(S360_ERR_STATE, "bottom image not uploaded");
@@ -804,7 +803,7 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
                                          pk.packed.as<unsigned>(), pk.tiles.p, F.sc->botSph.as<uchar4>(), W, rowsB,
                                          F.tab.dev, 1, yfs, c->P.std_alpha_feather_size);
         }
-        launch_extend_wrap(st, F.sc->botSph.as<uchar4>(), nullptr, W, rowsB, ext + 5 * xs, extW);
+        launch_extend_wrap(st, F.sc->botSph.as<uchar4>(), nullptr, W, rowsB, ext + L.fisheye(2), extW);
       }
     }
     {
@@ -818,7 +817,7 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
       for (int u = 0; u < 4; ++u)
         if (pole_mask & (1 << u)) {
           const uchar4* side = (u < 2) ? F.pano[u & 1].as<uchar4>() : F.sc->panoFlip[u & 1].as<uchar4>();
-          dev_feather_alpha_to_ext(c, side, W, rowsOf(u), ext + u * xs, extW);
+          dev_feather_alpha_to_ext(c, side, W, L.rows(u), ext + L.side(u), extW);
         }
     }
   }
@@ -853,14 +852,14 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
           const int pole = u >> 1;  // 0 top, 1 bottom
           if (fishIdx[pole] < 0) {
             fishIdx[pole] = (int)fb.images.size();
-            fb.images.push_back(ext + (4 + pole) * xs);
-            if (usePrev) fb.prev_images.push_back(pext + (4 + pole) * xs);
+            fb.images.push_back(ext + L.fisheye(u));
+            if (usePrev) fb.prev_images.push_back(pext + L.fisheye(u));
           }
           const int sideIdx = (int)fb.images.size();
-          fb.images.push_back(ext + u * xs);
-          if (usePrev) fb.prev_images.push_back(pext + u * xs);
-          fb.add_flow(sideIdx, fishIdx[pole], F.poleFlows.as<float2>() + u * xs,
-                      usePrev ? F.poleFlows.as<float2>() + u * xs : nullptr);
+          fb.images.push_back(ext + L.side(u));
+          if (usePrev) fb.prev_images.push_back(pext + L.side(u));
+          fb.add_flow(sideIdx, fishIdx[pole], F.poleFlows.as<float2>() + L.side(u),
+                      usePrev ? F.poleFlows.as<float2>() + L.side(u) : nullptr);
         }
       }
       c->flow_pole->compute(st, pc, fb, extW, rows, S360_HINT_DOWN);
@@ -887,23 +886,20 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
             // (frame_gather_pole_layers zeroes them itself for the layers it receives)
             SlotScratch& S = *F.sc;
             S.poleWarped[u].ensure(en * sizeof(uchar4));
-            const size_t padFrom = (size_t)W * std::min(rowsOf(u), H) * sizeof(uchar4), padTo = en * sizeof(uchar4);
+            const size_t padFrom = (size_t)W * std::min(L.rows(u), H) * sizeof(uchar4), padTo = en * sizeof(uchar4);
             if (S.polePadBuf[u] != S.poleWarped[u].p || S.polePadFrom[u] != padFrom || S.polePadTo[u] != padTo) {
               if (padTo > padFrom) S360_HIP(hipMemsetAsync(S.poleWarped[u].as<uint8_t>() + padFrom, 0, padTo - padFrom, st));
               S.polePadBuf[u] = S.poleWarped[u].p;
               S.polePadFrom[u] = padFrom;
               S.polePadTo[u] = padTo;
             }
-            dev_pole_unit_post(c, ext + (u < 2 ? 4 : 5) * xs, F.poleFlows.as<float2>() + u * xs, W, rowsOf(u), extW,
+            dev_pole_unit_post(c, ext + L.fisheye(u), F.poleFlows.as<float2>() + L.side(u), W, L.rows(u), extW,
                                S.poleWarped[u].as<uchar4>(), H, false);
             F.poleFrame[u] = F.frames_done;
             F.sc->poleOwner[u] = &F;
           }
       }
-      F.extW = extW;
-      F.extStride = xs;
-      F.poleRowsT = rowsT;
-      F.poleRowsB = rowsB;
+      L.stamp_pole(F);
       F.have_prev_pole = true;
       F.last_pole = cur;
       for (unsigned char& got : F.prevPoleGot) got = 0;

@@ -1,5 +1,6 @@
 // render.hpp — device-resident per-frame pipeline state (renderStereoPanorama, TRSP:716-972).
 #pragma once
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -107,8 +108,7 @@ struct FrameState {
   int prevPrW = 0, prevPrH = 0;  // size of the pole-removal images handed in as files
   bool keep_intermediates = false;  // copy panoramas before the pole composite (parity tests)
   DevBuf panoDbg[2];
-  int extW = 0, poleRowsT = 0, poleRowsB = 0;  // geometry the pole temporal state was produced with
-  size_t extStride = 0;                        // pixels between the slots of extImgs / poleFlows (extW * max rows)
+  int extW = 0, poleRowsT = 0, poleRowsB = 0;  // geometry the pole temporal state was produced with (its layout: PrevLayout below)
   // pole removal: secondary bottom source (BGRA), red-mask planes, flow inputs [cur/prev][2][n], flow [cur/prev][n]
   DevBuf botSrc2, prRed[2], prImgs[2], prFlow[2], prTmp, prWarp, prMerged;
   bool have_pr_inputs = false, have_prev_pr = false;
@@ -123,6 +123,38 @@ struct FrameState {
   DevBuf cubePngFile[2], cubePngMeta[2];
   PngPlan cubePngPlan[2];
   long long cubePngFrame[2] = {-1, -1};
+};
+
+// kExtendFrac (TRSP:400-401, 507): the pole stage's images are the panorama extended to this many widths, x % cols
+constexpr float kExtendFrac = 1.2f;
+inline int extended_width(int cols) { return int(float(cols) * kExtendFrac); }
+
+// Where a slot's temporal state lies — the one description that the stages that write it (frame_render_pairs, the finish stage)
+// and the entry points that hand it in or read it back (s360_frame_set_prev_*, s360_frame_get_*) share. Offsets are in pixels.
+//   overlaps[cur/prev] / sideFlows: the block [p0, p0 + n) of pairs: L images / LtoR flows of the block first, then R / RtoL
+//   extImgs[cur/prev]: six slots of `xs` pixels: the extended side images of pole units 0-3 (0 top_left, 1 top_right,
+//                      2 bottom_left, 3 bottom_right), then the top and the bottom extended fisheye image
+//   poleFlows: four slots of `xs` pixels, one per unit
+struct PrevLayout {
+  size_t on;              // one overlap image / side flow
+  int p0, n;
+  int extW, rowsT, rowsB;
+  size_t xs;              // slot stride of extImgs / poleFlows: room for the taller pole
+  explicit PrevLayout(const s360_ctx* c, int p0_ = 0, int p1 = 0)  // (no pairs: the pole half alone)
+      : on((size_t)c->g.overlap_image_width * c->g.cam_image_height), p0(p0_), n(p1 - p0_), extW(extended_width(c->P.eqr_width)),
+        rowsT(c->g.top_rows), rowsB(c->g.bottom_rows), xs((size_t)extW * std::max(rowsT, rowsB)) {}
+  size_t left(int j) const { return on * j; }         // pair p0 + j: overlap_l / flow_l_to_r
+  size_t right(int j) const { return on * (n + j); }  // ... overlap_r / flow_r_to_l
+  int rows(int unit) const { return unit < 2 ? rowsT : rowsB; }
+  size_t unit_pixels(int unit) const { return (size_t)extW * rows(unit); }
+  size_t side(int unit) const { return xs * unit; }                   // extended side image of a unit; also its flow in poleFlows
+  size_t fisheye(int unit) const { return xs * (unit < 2 ? 4 : 5); }  // the fisheye image is shared by the two units of a pole
+  size_t overlaps_bytes() const { return 2 * n * on * sizeof(uchar4); }
+  size_t side_flows_bytes() const { return 2 * n * on * sizeof(float2); }
+  size_t ext_bytes() const { return 6 * xs * sizeof(uchar4); }
+  size_t pole_flows_bytes() const { return 4 * xs * sizeof(float2); }
+  // the geometry the pole state of F was produced with (what the getters report and the finish stage compares)
+  void stamp_pole(FrameState& F) const { F.extW = extW; F.poleRowsT = rowsT; F.poleRowsB = rowsB; }
 };
 
 FrameState& frame_state(s360_ctx* c);

@@ -35,5 +35,5 @@ extern "C" int emu_isp_run(const s360_isp_config* cfg, const uint16_t* raw, int 
   }
 }
 
-// (isp.cpp asks api.hip whether the context an ISP object is bound to still lives; this tool has no contexts)
+// (isp.cpp asks api.hip's context registry whether the context an ISP object is bound to still lives; this tool has no contexts)
 namespace s360 { bool context_alive(unsigned long long) { return true; } }
