@@ -71,6 +71,13 @@ struct Flags {
          // inflating them (png_io.hpp) and their pixels being uploaded. A file the device decoder does not take (cv::imwrite's,
          // the reference program's) takes the host path for its pair or unit. Same state on the device either way.
          {"device_state_read", "false"},
+         // --device_input_png (default off; S360_DEVICE_INPUT_PNG=1 in the environment switches it on too): the camera images of
+         // imgs_dir are read as bytes, and those the device decoder takes with colour type 2 (s360_input_png_decodable: the banded
+         // files Unpacker --device_png and Raw2Rgb --device_png write, 16- or 8-bit) go to every GPU context that needs them in
+         // ONE s360_frame_upload_png, which writes the frame's source slots from the files, instead of host threads inflating them
+         // and their pixels being uploaded. Every other file (cv::imwrite's, RGBA, JPEG, interlaced) takes the host decoder and
+         // the pixel upload as before, file by file. Same files written either way. Ignored with --bin_list.
+         {"device_input_png", "false"},
          // --num_gpus G: the 14 side pairs of the frame sharded over G GPUs, one RCCL strip gather
          {"num_gpus", "1"},
          // --num_frames N: frames frame_number .. +N-1 as ONE stream in this process (temporal state stays on the
@@ -96,7 +103,8 @@ struct Flags {
   }
   static bool is_bool(const std::string& k) {
     static const char* b[] = {"save_debug_images", "enable_top", "enable_bottom", "enable_pole_removal", "logtostderr",
-                              "alsologtostderr", "write_state", "soft_isp", "device_png", "device_state_png", "device_state_read"};
+                              "alsologtostderr", "write_state", "soft_isp", "device_png", "device_state_png", "device_state_read",
+                              "device_input_png"};
     for (auto s : b)
       if (k == s) return true;
     return false;
@@ -224,6 +232,9 @@ struct FrameInputs {
   std::string frame;
   std::vector<pngio::Image> side;
   pngio::Image top, bottom, bottom2, mask1, mask2;
+  // --device_input_png: the file of a camera whose image the device decodes (its pngio::Image then holds the size only); else empty
+  std::vector<std::vector<uint8_t>> sideFile;
+  std::vector<uint8_t> topFile, bottomFile;
   long binFrame = -1;  // --bin_list: the frame's index in the containers (nothing is decoded on the host)
 };
 // --bin_list: where a rig camera's frames are, and the ISP that develops them
@@ -273,6 +284,31 @@ void assign_pole_units(Job& J) {
   J.need[0] = 3;  // the root composites both eyes
 }
 
+// --device_input_png: how many camera files took which path (--v 1)
+std::atomic<int> g_inputOnDevice(0), g_inputOnHost(0);
+bool device_input_png(const Flags& F) {
+  const char* e = std::getenv("S360_DEVICE_INPUT_PNG");
+  return F.s("bin_list").empty() && (F.b("device_input_png") || (e && !std::strcmp(e, "1")));
+}
+std::vector<uint8_t> read_bytes(const std::string& path);
+// One camera's image: with --device_input_png its file's bytes if the device decoder takes them as a 3-channel image (`file`
+// keeps them, `im` gets the size only), else the pixels as the host decodes them.
+void load_camera_image(bool device, const std::string& path, pngio::Image& im, std::vector<uint8_t>& file) {
+  file.clear();
+  if (device) {
+    file = read_bytes(path);
+    int info[5] = {0, 0, 0, 0, 0};
+    if (s360_input_png_decodable(file.data(), file.size(), info) == S360_OK && info[2] == 3) {
+      im.w = info[0]; im.h = info[1]; im.c = 3;  // (the size is known, e.g. to the pole-removal check; no pixels on the host)
+      ++g_inputOnDevice;
+      return;
+    }
+    file.clear();
+    ++g_inputOnHost;
+  }
+  load_png_into(path, false, im);
+}
+
 // `recycled`: the inputs of an earlier frame whose pixel buffers are reused (stream mode)
 FrameInputs load_frame(const Job& J, const std::string& frame, FrameInputs recycled = FrameInputs()) {
   FrameInputs in = std::move(recycled);
@@ -284,16 +320,18 @@ FrameInputs load_frame(const Job& J, const std::string& frame, FrameInputs recyc
     return in;
   }
   in.side.resize(J.P);
+  in.sideFile.resize(J.P);
+  const bool dev = device_input_png(J.F);
   const std::string imgs = J.F.s("imgs_dir");
   std::vector<std::thread> th;
   for (int k = 0; k < J.P; ++k)
     th.emplace_back([&, k] {
       const std::string dir = imgs + "/" + J.cams[J.sideIdx[k]].id;
-      load_png_into(dir + "/" + frame + image_extension(dir), false, in.side[k]);
+      load_camera_image(dev, dir + "/" + frame + image_extension(dir), in.side[k], in.sideFile[k]);
     });
-  if (J.prm.enable_top) th.emplace_back([&] { load_png_into(imgs + "/" + J.cams[J.ti].id + "/" + frame + ".png", false, in.top); });  // TRSP:652
+  if (J.prm.enable_top) th.emplace_back([&] { load_camera_image(dev, imgs + "/" + J.cams[J.ti].id + "/" + frame + ".png", in.top, in.topFile); });  // TRSP:652
   if (J.prm.enable_bottom) {
-    th.emplace_back([&] { load_png_into(imgs + "/" + J.cams[J.bi].id + "/" + frame + ".png", false, in.bottom); });  // TRSP:602
+    th.emplace_back([&] { load_camera_image(dev, imgs + "/" + J.cams[J.bi].id + "/" + frame + ".png", in.bottom, in.bottomFile); });  // TRSP:602
     if (J.prm.enable_pole_removal) {  // PoleRemoval.cpp:48-66
       const std::string masks = J.F.s("bottom_pole_masks_dir");
       th.emplace_back([&] { in.bottom2 = load_png(imgs + "/" + J.cams[J.b2].id + "/" + frame + ".png", false); });
@@ -333,14 +371,28 @@ void upload_frame(const Job& J, const FrameInputs& in) {
   for (int r = 0; r < G; ++r) {
     std::vector<char> need(J.P, 0);
     for (int p = J.bounds[r]; p < J.bounds[r + 1]; ++p) need[p] = need[(p + 1) % J.P] = 1;
+    // --device_input_png: the cameras of this GPU whose files the device decodes, in one call (synchronous; a damaged file dies
+    // here like a file the host decoder cannot read)
+    std::vector<int> cams;
+    std::vector<const uint8_t*> files;
+    std::vector<size_t> bytes;
+    auto by_file = [&](int camera, const std::vector<uint8_t>& f) {
+      if (f.empty()) return false;
+      cams.push_back(camera); files.push_back(f.data()); bytes.push_back(f.size());
+      return true;
+    };
     for (int k = 0; k < J.P; ++k)
-      if (need[k]) ck(s360_frame_upload_side(J.ctx[r], k, in.side[k].px.data(), in.side[k].w, in.side[k].h, in.side[k].c), J.ctx[r]);
+      if (need[k] && !by_file(k, in.sideFile[k]))
+        ck(s360_frame_upload_side(J.ctx[r], k, in.side[k].px.data(), in.side[k].w, in.side[k].h, in.side[k].c), J.ctx[r]);
+    if (J.unitMask[r] & 3) by_file(S360_CAMERA_TOP, in.topFile);
+    if (J.unitMask[r] & 12) by_file(S360_CAMERA_BOTTOM, in.bottomFile);
+    if (!cams.empty()) ck(s360_frame_upload_png(J.ctx[r], (int)cams.size(), cams.data(), files.data(), bytes.data()), J.ctx[r]);
   }
   for (int r = 0; r < G; ++r) {  // the pole images go to the GPUs that run units of that pole
     s360_ctx* c = J.ctx[r];
-    if (J.unitMask[r] & 3) ck(s360_frame_upload_top(c, in.top.px.data(), in.top.w, in.top.h), c);
+    if ((J.unitMask[r] & 3) && in.topFile.empty()) ck(s360_frame_upload_top(c, in.top.px.data(), in.top.w, in.top.h), c);
     if (J.unitMask[r] & 12) {
-      ck(s360_frame_upload_bottom(c, in.bottom.px.data(), in.bottom.w, in.bottom.h), c);
+      if (in.bottomFile.empty()) ck(s360_frame_upload_bottom(c, in.bottom.px.data(), in.bottom.w, in.bottom.h), c);
       if (J.prm.enable_pole_removal)
         ck(s360_frame_upload_pole_removal(c, in.bottom2.px.data(), in.mask1.px.data(), in.mask2.px.data(), in.bottom.w, in.bottom.h), c);
     }
@@ -1191,6 +1243,9 @@ static int run_job(const Flags& flags) {
                    tDecode / nf, tUpload / nf, tFetch / nf, tJoin / nf, per - (tDecode + tUpload + tFetch + tJoin) / nf, per,
                    numFrames - nf, numFrames - 1);
     }
+    if (device_input_png(F))
+      std::fprintf(stderr, "camera images:           %d files decoded on the device, %d on the host (--device_input_png)\n", g_inputOnDevice.load(),
+                   g_inputOnHost.load());
     std::fprintf(stderr, "TOTAL:                   %.3f\n", endTime - startTime);
   }
   if (g_fast_exit) return 0;  // main leaves the process at once (one frame per process): the device memory goes with it
@@ -1404,6 +1459,9 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
     if (later > 0 && endTime > tStep0)
       std::fprintf(stderr, "steady state:            %d frames of steps 1..%d in %.3f  (%.2f frames per second, files written)\n", later, steps - 1,
                    endTime - tStep0, later / (endTime - tStep0));
+    if (device_input_png(flags))
+      std::fprintf(stderr, "camera images:           %d files decoded on the device, %d on the host (--device_input_png)\n", g_inputOnDevice.load(),
+                   g_inputOnHost.load());
     std::fprintf(stderr, "TOTAL:                   %.3f\n", endTime - startTime);
   }
   for (auto& kv : J.binCam)

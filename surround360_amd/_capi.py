@@ -104,6 +104,8 @@ PNG_DECODE_SYMBOLS = [
 ISP_PNG_SYMBOLS = [
     "s360_png_bound_16", "s360_encode_png16", "s360_isp_png_bound", "s360_isp_process_png", "s360_isp_process_packed_png",
 ]
+# ... and every symbol include/s360_input_png.h declares (camera images as banded PNG files, 8- or 16-bit, decoded on the device)
+INPUT_PNG_SYMBOLS = ("s360_input_png_decodable", "s360_decode_input_png_batch", "s360_frame_upload_png")
 # ... and the test taps include/s360_debug.h declares (not part of the API)
 DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
 # ... and the one include/s360_debug_final_flow.h declares
@@ -215,6 +217,13 @@ def lib():
         L.s360_isp_process_packed_png.restype = C.c_int
         L.s360_isp_process_packed_png.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                                   C.POINTER(C.c_size_t)]
+        L.s360_input_png_decodable.restype = C.c_int
+        L.s360_input_png_decodable.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+        L.s360_decode_input_png_batch.restype = C.c_int
+        L.s360_decode_input_png_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                  C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int)]
+        L.s360_frame_upload_png.restype = C.c_int
+        L.s360_frame_upload_png.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
         L.s360_debug_isp_stages.restype = C.c_int
         L.s360_debug_isp_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8
         L.s360_debug_flow_level.restype = C.c_int

@@ -1,5 +1,5 @@
 // api_png.hip — fetching what a finished frame left on the device, and the PNG family of the C ABI (include/s360.h,
-// s360_cubemap.h, s360_state_png.h, s360_png_decode.h, s360_isp_png.h): downloads by age and slot, frames / cubemaps / state images
+// s360_cubemap.h, s360_state_png.h, s360_png_decode.h, s360_isp_png.h, s360_input_png.h): downloads by age and slot, frames / cubemaps / state images
 // as PNG files encoded on the device (png.hip), banded PNG files decoded on the device (png_decode.hip).
 #include <algorithm>
 #include <cstdlib>
@@ -377,13 +377,13 @@ int s360_png_decodable(const uint8_t* file, size_t n, int whc[3], int* band_rows
   c->pngDecFailReason = reason;
   throw Error(S360_ERR_INVALID_ARG, msg);
 }
-static std::vector<PngBandedInfo> png_parse_all(s360_ctx* c, int n, const uint8_t* const* files, const size_t* bytes) {
+static std::vector<PngBandedInfo> png_parse_all(s360_ctx* c, int n, const uint8_t* const* files, const size_t* bytes, bool input = false) {
   c->pngDecFailImage = -1;
   c->pngDecFailReason = S360_PNG_DECODE_FAILURE_NONE;
   std::vector<PngBandedInfo> info((size_t)n);
   for (int i = 0; i < n; ++i) {
     need(files[i] != nullptr, "bad argument");
-    if (!png_parse_banded(files[i], bytes[i], info[(size_t)i]))
+    if (!(input ? png_parse_banded_input : png_parse_banded)(files[i], bytes[i], info[(size_t)i]))
       png_fail(c, i, S360_PNG_DECODE_FAILURE_NOT_DECODABLE, "png decode: image " + std::to_string(i) + ": " + kNotDecodable);
   }
   return info;
@@ -509,6 +509,86 @@ int s360_frame_set_prev_images_png(s360_ctx* c, int n, const char* const* names,
         F.prevPrW = prW; F.prevPrH = prH;
         prev_pr_arrived(F, a.bits);
       }
+    }
+  });
+}
+/* ---- camera images as banded PNG files, 8- or 16-bit, decoded on the device (include/s360_input_png.h) ---- */
+static void input_png_info(const PngBandedInfo& I, int* info) {
+  info[0] = I.w; info[1] = I.h; info[2] = I.channels; info[3] = I.depth; info[4] = I.band_rows;
+}
+int s360_input_png_decodable(const uint8_t* file, size_t n, int info[5]) {
+  return guard([&] {
+    need(info != nullptr, "bad argument");
+    PngBandedInfo I;
+    if (!png_parse_banded_input(file, n, I)) throw Error(S360_ERR_INVALID_ARG, kNotDecodable);
+    input_png_info(I, info);
+  });
+}
+int s360_decode_input_png_batch(s360_ctx* c, int n, const uint8_t* const* files, const size_t* bytes, void* const* out, const size_t* cap_bytes,
+                                int keep16, int* info_out) {
+  if (!c) return S360_ERR_INVALID_ARG;
+  return guard_l(c, [&](std::unique_lock<std::recursive_mutex>&) {
+    need(n > 0 && n <= 4096 && files && bytes && out && cap_bytes, "bad argument");
+    const std::vector<PngBandedInfo> info = png_parse_all(c, n, files, bytes, true);
+    std::vector<size_t> at, nbytes;
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+      const PngBandedInfo& I = info[(size_t)i];
+      const bool u16 = I.depth == 16 && keep16;
+      const size_t nb = (size_t)I.w * I.h * I.channels * (u16 ? 2 : 1);
+      need(out[i] != nullptr, "bad argument");
+      if (cap_bytes[i] < nb) png_fail(c, i, S360_PNG_DECODE_FAILURE_MISMATCH, "png decode: image " + std::to_string(i) + ": output buffer too small");
+      if (u16 && (reinterpret_cast<uintptr_t>(out[i]) & 1))
+        png_fail(c, i, S360_PNG_DECODE_FAILURE_MISMATCH, "png decode: image " + std::to_string(i) + ": 16-bit output not 2-byte aligned");
+      at.push_back(total);
+      nbytes.push_back(nb);
+      total += (nb + 15) & ~(size_t)15;
+    }
+    c->op_a.ensure(total);
+    std::vector<PngDecodeDst> dst((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      dst[(size_t)i].p = c->op_a.as<uint8_t>() + at[(size_t)i];
+      dst[(size_t)i].store = info[(size_t)i].depth == 16 && keep16 ? kPngStoreU16 : kPngStoreBytes;
+    }
+    try {
+      png_decode_run(c->st, c->pngDec, std::vector<const uint8_t*>(files, files + n), info, dst, {}, c->pngDecStats, &c->prof);
+    } catch (const PngDecodeError& e) {
+      c->pngDecFailImage = e.image;
+      c->pngDecFailReason = S360_PNG_DECODE_FAILURE_DAMAGED;
+      throw;
+    }
+    for (int i = 0; i < n; ++i) {
+      S360_HIP(hipMemcpyAsync(out[i], dst[(size_t)i].p, nbytes[(size_t)i], hipMemcpyDeviceToHost, c->st));
+      if (info_out) input_png_info(info[(size_t)i], info_out + 5 * i);
+    }
+    S360_HIP(hipStreamSynchronize(c->st));
+  }, false);
+}
+int s360_frame_upload_png(s360_ctx* c, int n, const int* cameras, const uint8_t* const* files, const size_t* bytes) {
+  return frame_guard(c, [&] {
+    need(c && n > 0 && n <= 66 && cameras && files && bytes, "bad argument");
+    FrameState& F = frame_state(c);
+    need(F.P <= 64, "more than 64 side cameras");
+    for (int i = 0; i < n; ++i) {
+      need(cameras[i] >= S360_CAMERA_BOTTOM && cameras[i] < F.P, "camera index out of range");
+      for (int j = 0; j < i; ++j) need(cameras[j] != cameras[i], "a camera is named twice");
+    }
+    const std::vector<PngBandedInfo> info = png_parse_all(c, n, files, bytes, true);
+    int sw = F.have_side ? F.srcW : 0, sh = F.have_side ? F.srcH : 0;
+    for (int i = 0; i < n; ++i) {
+      const PngBandedInfo& I = info[(size_t)i];
+      if (I.channels != 3)
+        png_fail(c, i, S360_PNG_DECODE_FAILURE_MISMATCH, "png decode: image " + std::to_string(i) + ": a camera image must have colour type 2 (3 channels)");
+      if (cameras[i] < 0) continue;
+      if (!sw) { sw = I.w; sh = I.h; }
+      if (I.w != sw || I.h != sh) png_fail(c, i, S360_PNG_DECODE_FAILURE_MISMATCH, "png decode: image " + std::to_string(i) + ": side image size changed");
+    }
+    try {
+      frame_upload_png(c, std::vector<int>(cameras, cameras + n), std::vector<const uint8_t*>(files, files + n), info);
+    } catch (const PngDecodeError& e) {
+      c->pngDecFailImage = e.image;
+      c->pngDecFailReason = S360_PNG_DECODE_FAILURE_DAMAGED;
+      throw;
     }
   });
 }

@@ -49,7 +49,7 @@
 // 2 (2 - s) + (1 - (k & 1)) (src_byte); Sub at a distance of 6 bytes, line = 1 + 6 w, a tile is 2048 pixels. A row of an odd-width image
 // starts on a 2-byte boundary only: load_tile takes dwords from the aligned address below, as it does for 3 w. The camera images of
 // the unpack step (host/Unpacker --device_png: png_encode_enqueue behind the ISP's kernels on the ISP object's stream, api_isp.hip). The
-// batch kernel and the decoder (png_decode.hip) stay 8-bit.
+// batch kernel stays 8-bit; the decoder (png_decode.hip) reads these files back through layout 6 of k_png_unfilter (s360_input_png.h).
 // Batch. C = 0 is the kernel over the bands of MANY images of differing size and channel count (png_batch_enqueue): a device table
 // holds one descriptor per image and the image index of every band, a workgroup looks its band up and runs the C = 3 or C = 4 body.
 // One band launch, one layout launch (a workgroup per image: the prefix sum is segmented), one gather launch; every image gets a

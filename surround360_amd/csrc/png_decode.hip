@@ -33,6 +33,16 @@
 //   along the row = a wave scan over the pixels' dwords with byte-wise adds, the waves' totals and the tile's carry through LDS;
 //   type 0 rows are copied; R and B swap on the way out, alpha stays; any other filter type sets the band's status (unsupported,
 //   as the host's parallel reader bails out). It also sums the band's Adler-32 pieces (s1, s2) for the host to combine.
+//   The band's image picks one instantiation of unfilter_band<layout, store>. Layouts: 3 and 4 bytes per pixel (8-bit R,G,B(,A)) and
+//   6 (16-bit R,G,B, high byte first, Sub at a distance of 6: what k_png_band<6> of png.hip writes for the camera images); a pixel's
+//   6 bytes start at any byte offset and are loaded as two or three dwords, each of which holds a byte of that pixel. Stores: packed
+//   8-bit B,G,R(,A) (a 16-bit file keeps its high bytes: png_set_strip_16), packed little-endian uint16 B,G,R, and a frame's source
+//   slots written directly — a side slot, uchar4 with side_src_alpha's row ramp (render_kernels.hpp, shared with
+//   k_prepare_side_src), and a pole slot, uchar4 with alpha 255 — with no B,G,R intermediate (s360_frame_upload_png). The Adler-32
+//   is over all 6 bytes whatever the store keeps; the stores that keep high bytes scan byte lanes 0, 2, 4 packed into one dword.
+//   Resources (gfx950, -Rpass-analysis=kernel-resource-usage): 45 VGPRs, 71 SGPRs, 40 bytes of LDS, no scratch, 8 waves per SIMD
+//   (with layouts 3 and 4 alone: 43 VGPRs, 76 SGPRs, 24 bytes of LDS); k_png_inflate is unchanged at 181 VGPRs, 106 SGPRs,
+//   21 884 bytes of LDS, no scratch.
 //   Two kernels, not one: the fused form (unfilter out of the LDS window) was not built, so there is no measurement of it.
 // Measured (profiles/state_png_read.txt, the 36 state images of an 8K frame, 6000 bands, all on the fast path): k_png_inflate
 // 85.5-86.7 ms, k_png_unfilter 0.76 ms. The round count (rounds up to the last one in which a lane decoded again, + 1) says why the
@@ -46,6 +56,7 @@
 #include <string>
 
 #include "../../include/s360.h"
+#include "render_kernels.hpp"
 
 namespace s360 {
 
@@ -72,8 +83,9 @@ struct DecBand {
 };
 struct DecImage {
   uint8_t* dst;
-  int w, h, channels;
+  int w, h, pix;  // pix: bytes per pixel in the file (3, 4, or 6 for 16-bit R,G,B)
   unsigned line;
+  int store, feather;  // PngStore; kPngStoreSide: side_alpha_feather_size
 };
 struct DecOut {
   unsigned status, s1, s2, path, rounds, pad;  // path: 1 fast, 2 general, 3 stored blocks only
@@ -568,64 +580,97 @@ __device__ inline unsigned badd(unsigned a, unsigned b) {  // four byte-wise sum
   return ((a & 0x7f7f7f7fu) + (b & 0x7f7f7f7fu)) ^ ((a ^ b) & 0x80808080u);
 }
 constexpr int kUT = 256;
-__global__ __launch_bounds__(kUT) void k_png_unfilter(const uint8_t* __restrict__ filt, const DecBand* __restrict__ bands,
-                                                       const DecImage* __restrict__ imgs, DecOut* __restrict__ outs) {
-  __shared__ unsigned wtot[kUT / 64];
-  __shared__ unsigned acc[2];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-  if (outs[b].status) return;
-  const DecBand B = bands[b];
-  const DecImage I = imgs[B.img];
-  const unsigned C = (unsigned)I.channels, line = I.line, n = B.n;
-  const uint8_t* src = filt + B.filt_off;  // 16-byte aligned
-  const unsigned* srcw = reinterpret_cast<const unsigned*>(src);
-  if (t < 2) acc[t] = 0u;
+// Sub over one tile of a row: x[] becomes the byte-wise running sum of the pixels up to this thread's (a wave scan, the waves' totals
+// and the tile's carry through LDS), carry[] the sum up to the tile's last pixel. NX dwords per pixel, every byte a lane of its own.
+template <int NX>
+__device__ inline void sub_scan(unsigned (&x)[NX], unsigned (&carry)[NX], unsigned (*wtot)[kUT / 64], int lane, int wv) {
+  for (int d = 1; d < 64; d <<= 1)
+    for (int k = 0; k < NX; ++k) {
+      const unsigned q = (unsigned)__builtin_amdgcn_ds_bpermute(((lane - d) & 63) << 2, (int)x[k]);
+      if (lane >= d) x[k] = badd(x[k], q);
+    }
+  if (lane == 63)
+    for (int k = 0; k < NX; ++k) wtot[k][wv] = x[k];
   __syncthreads();
+  for (int k = 0; k < NX; ++k) {
+    unsigned pre = carry[k], all = carry[k];
+    for (int j = 0; j < kUT / 64; ++j) {
+      if (j < wv) pre = badd(pre, wtot[k][j]);
+      all = badd(all, wtot[k][j]);
+    }
+    x[k] = badd(x[k], pre);
+    carry[k] = all;
+  }
+  __syncthreads();
+}
+// One band of an image of L bytes per pixel (3: R,G,B; 4: R,G,B,A; 6: R,G,B of 16 bits, high byte first) into store S. The
+// Adler-32 pieces are over every byte of the scanlines whatever the store keeps. Sub has no carries between byte lanes, so the
+// stores that keep a 16-bit file's high bytes scan byte lanes 0, 2 and 4 only, packed into one dword: the scan of layout 3.
+template <int L, int S>
+__device__ inline void unfilter_band(const uint8_t* __restrict__ src, const DecBand& B, const DecImage& I, DecOut* __restrict__ out,
+                                     unsigned (*wtot)[kUT / 64], unsigned* acc) {
+  constexpr int NX = (L == 6 && S == kPngStoreU16) ? 2 : 1;
+  static_assert(S == kPngStoreBytes || (S == kPngStoreU16 && L == 6) || ((S == kPngStoreSide || S == kPngStorePole) && L != 4), "no such store");
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const unsigned line = I.line, n = B.n;
+  const unsigned* srcw = reinterpret_cast<const unsigned*>(src);  // 16-byte aligned, padded to 16 bytes behind n
   unsigned long long sum = 0, wsum = 0;
   for (unsigned r = 0; r < B.rows; ++r) {
     const unsigned rowoff = r * line;
     const unsigned f = src[rowoff];
     if (f > 1u) {  // (the same for every thread)
-      if (t == 0) outs[b].status = kBadFilter;
+      if (t == 0) out->status = kBadFilter;
       return;
     }
     if (t == 0) { sum += f; wsum += (unsigned long long)(n - rowoff) * f; }
-    const size_t drow = (size_t)(B.y0 + r) * (size_t)I.w;
-    unsigned carry = 0;
+    const int y = (int)(B.y0 + r);
+    const size_t drow = (size_t)y * (size_t)I.w;
+    const unsigned alpha = S == kPngStoreSide ? (unsigned)side_src_alpha(y, I.h, I.feather, 255) : 255u;
+    unsigned carry[NX] = {};
     for (int p0 = 0; p0 < I.w; p0 += kUT) {
       const int p = p0 + t;
-      unsigned v = 0;
+      unsigned x[NX] = {};
       if (p < I.w) {
-        const unsigned boff = rowoff + 1u + C * (unsigned)p, sh = 8u * (boff & 3u);
-        const unsigned lo = srcw[boff >> 2], hi = (boff & 3u) + C > 4u ? srcw[(boff >> 2) + 1u] : 0u;
-        v = (unsigned)(((((unsigned long long)hi) << 32) | lo) >> sh);
-        if (C == 3u) v &= 0xffffffu;
-        const unsigned b0 = v & 255u, b1 = (v >> 8) & 255u, b2 = (v >> 16) & 255u, b3 = v >> 24, s = b0 + b1 + b2 + b3;
-        sum += s;
-        wsum += (unsigned long long)(n - boff) * s - (b1 + 2u * b2 + 3u * b3);
-      }
-      unsigned x = v;
-      if (f == 1u) {  // Sub: the running sum of the pixels to the left, per channel
-        for (int d = 1; d < 64; d <<= 1) {
-          const unsigned q = (unsigned)__builtin_amdgcn_ds_bpermute(((lane - d) & 63) << 2, (int)x);
-          if (lane >= d) x = badd(x, q);
+        const unsigned boff = rowoff + 1u + (unsigned)L * (unsigned)p, sh = 8u * (boff & 3u), wi = boff >> 2;
+        const unsigned w0 = srcw[wi];
+        if (L == 6) {
+          // 6 bytes from any byte offset: two dwords, a third only where the pixel reaches into it (every dword read holds a
+          // byte of this pixel, so none lies behind the band's padded scanlines)
+          const unsigned w1 = srcw[wi + 1u], w2 = (boff & 3u) == 3u ? srcw[wi + 2u] : 0u;
+          const unsigned lo = (unsigned)(((((unsigned long long)w1) << 32) | w0) >> sh);
+          const unsigned hi = (unsigned)(((((unsigned long long)w2) << 32) | w1) >> sh) & 0xffffu;
+          const unsigned b0 = lo & 255u, b1 = (lo >> 8) & 255u, b2 = (lo >> 16) & 255u, b3 = lo >> 24, b4 = hi & 255u, b5 = hi >> 8;
+          const unsigned s = b0 + b1 + b2 + b3 + b4 + b5;
+          sum += s;
+          wsum += (unsigned long long)(n - boff) * s - (b1 + 2u * b2 + 3u * b3 + 4u * b4 + 5u * b5);
+          if (NX == 2) { x[0] = lo; x[NX - 1] = hi; }
+          else x[0] = b0 | (b2 << 8) | (b4 << 16);
+        } else {
+          const unsigned hi = (boff & 3u) + (unsigned)L > 4u ? srcw[wi + 1u] : 0u;
+          unsigned v = (unsigned)(((((unsigned long long)hi) << 32) | w0) >> sh);
+          if (L == 3) v &= 0xffffffu;
+          const unsigned b0 = v & 255u, b1 = (v >> 8) & 255u, b2 = (v >> 16) & 255u, b3 = v >> 24, s = b0 + b1 + b2 + b3;
+          sum += s;
+          wsum += (unsigned long long)(n - boff) * s - (b1 + 2u * b2 + 3u * b3);
+          x[0] = v;
         }
-        if (lane == 63) wtot[wv] = x;
-        __syncthreads();
-        unsigned pre = carry, all = carry;
-        for (int k = 0; k < kUT / 64; ++k) {
-          if (k < wv) pre = badd(pre, wtot[k]);
-          all = badd(all, wtot[k]);
-        }
-        x = badd(x, pre);
-        carry = all;
-        __syncthreads();
       }
+      if (f == 1u) sub_scan<NX>(x, carry, wtot, lane, wv);
       if (p < I.w) {
-        if (C == 4u) reinterpret_cast<unsigned*>(I.dst)[drow + (size_t)p] = (x & 0xff00ff00u) | ((x >> 16) & 255u) | ((x & 255u) << 16);
-        else {
+        const unsigned v = x[0];  // bytes R, G, B (, A)
+        if (S == kPngStoreU16) {
+          const unsigned h2 = x[NX - 1];
+          unsigned short* o = reinterpret_cast<unsigned short*>(I.dst) + (drow + (size_t)p) * 3;
+          o[0] = (unsigned short)(((h2 & 255u) << 8) | ((h2 >> 8) & 255u));
+          o[1] = (unsigned short)(((v >> 8) & 0xff00u) | (v >> 24));
+          o[2] = (unsigned short)(((v & 255u) << 8) | ((v >> 8) & 255u));
+        } else if (S == kPngStoreSide || S == kPngStorePole) {
+          reinterpret_cast<unsigned*>(I.dst)[drow + (size_t)p] = (v & 0xff00u) | ((v >> 16) & 255u) | ((v & 255u) << 16) | (alpha << 24);
+        } else if (L == 4) {
+          reinterpret_cast<unsigned*>(I.dst)[drow + (size_t)p] = (v & 0xff00ff00u) | ((v >> 16) & 255u) | ((v & 255u) << 16);
+        } else {
           uint8_t* o = I.dst + (drow + (size_t)p) * 3;
-          o[0] = (uint8_t)(x >> 16); o[1] = (uint8_t)(x >> 8); o[2] = (uint8_t)x;
+          o[0] = (uint8_t)(v >> 16); o[1] = (uint8_t)(v >> 8); o[2] = (uint8_t)v;
         }
       }
     }
@@ -634,18 +679,48 @@ __global__ __launch_bounds__(kUT) void k_png_unfilter(const uint8_t* __restrict_
   atomicAdd(&acc[0], (unsigned)(sum % kAdler));
   atomicAdd(&acc[1], (unsigned)(wsum % kAdler));
   __syncthreads();
-  if (t == 0) { outs[b].s1 = acc[0] % kAdler; outs[b].s2 = acc[1] % kAdler; }
+  if (t == 0) { out->s1 = acc[0] % kAdler; out->s2 = acc[1] % kAdler; }
+}
+// A workgroup per band; the band's image says which instantiation runs (the same for every thread of the workgroup).
+__global__ __launch_bounds__(kUT) void k_png_unfilter(const uint8_t* __restrict__ filt, const DecBand* __restrict__ bands,
+                                                       const DecImage* __restrict__ imgs, DecOut* __restrict__ outs) {
+  __shared__ unsigned wtot[2][kUT / 64];
+  __shared__ unsigned acc[2];
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (outs[b].status) return;
+  const DecBand B = bands[b];
+  const DecImage I = imgs[B.img];
+  const uint8_t* src = filt + B.filt_off;  // 16-byte aligned
+  if (t < 2) acc[t] = 0u;
+  __syncthreads();
+  switch (I.store * 8 + I.pix) {
+    case kPngStoreBytes * 8 + 3: unfilter_band<3, kPngStoreBytes>(src, B, I, outs + b, wtot, acc); break;
+    case kPngStoreBytes * 8 + 4: unfilter_band<4, kPngStoreBytes>(src, B, I, outs + b, wtot, acc); break;
+    case kPngStoreBytes * 8 + 6: unfilter_band<6, kPngStoreBytes>(src, B, I, outs + b, wtot, acc); break;
+    case kPngStoreU16 * 8 + 6: unfilter_band<6, kPngStoreU16>(src, B, I, outs + b, wtot, acc); break;
+    case kPngStoreSide * 8 + 3: unfilter_band<3, kPngStoreSide>(src, B, I, outs + b, wtot, acc); break;
+    case kPngStoreSide * 8 + 6: unfilter_band<6, kPngStoreSide>(src, B, I, outs + b, wtot, acc); break;
+    case kPngStorePole * 8 + 3: unfilter_band<3, kPngStorePole>(src, B, I, outs + b, wtot, acc); break;
+    case kPngStorePole * 8 + 6: unfilter_band<6, kPngStorePole>(src, B, I, outs + b, wtot, acc); break;
+    default:  // (png_decode_run refuses every other pair)
+      if (t == 0) outs[b].status = kBadFilter;
+  }
 }
 
 inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+bool parse_banded(const uint8_t* file, size_t n, PngBandedInfo& info, bool allow16);
 }  // namespace
 
-bool png_parse_banded(const uint8_t* file, size_t n, PngBandedInfo& info) {
+bool png_parse_banded(const uint8_t* file, size_t n, PngBandedInfo& info) { return parse_banded(file, n, info, false); }
+bool png_parse_banded_input(const uint8_t* file, size_t n, PngBandedInfo& info) { return parse_banded(file, n, info, true); }
+
+namespace {
+bool parse_banded(const uint8_t* file, size_t n, PngBandedInfo& info, bool allow16) {
   static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
   if (!file || n < 8 || std::memcmp(file, sig, 8) != 0) return false;
   size_t pos = 8;
   uint32_t w = 0, h = 0, band_rows = 0;
-  int ctype = -1;
+  int ctype = -1, depth = 8;
   bool have_ihdr = false;
   std::vector<std::pair<size_t, size_t>> idat;
   while (pos + 12 <= n) {
@@ -657,8 +732,10 @@ bool png_parse_banded(const uint8_t* file, size_t n, PngBandedInfo& info) {
       if (len < 13) return false;
       w = be32(data); h = be32(data + 4);
       if (w == 0 || h == 0 || w > 65535u || h > 65535u) return false;
-      if (data[8] != 8 || (data[9] != 2 && data[9] != 6) || data[10] != 0 || data[11] != 0 || data[12] != 0) return false;
+      if ((data[9] != 2 && data[9] != 6) || data[10] != 0 || data[11] != 0 || data[12] != 0) return false;
+      if (data[8] != 8 && !(allow16 && data[8] == 16 && data[9] == 2)) return false;
       ctype = data[9];
+      depth = data[8];
       have_ihdr = true;
     } else if (!std::memcmp(type, "sbNd", 4) && len == 4) band_rows = std::min<uint32_t>(be32(data), 65535u);
     else if (!std::memcmp(type, "IDAT", 4)) idat.emplace_back(pos + 8, (size_t)len);
@@ -668,18 +745,26 @@ bool png_parse_banded(const uint8_t* file, size_t n, PngBandedInfo& info) {
   if (!have_ihdr || band_rows == 0 || idat.size() < 3 || idat[0].second != 2 || idat.back().second != 4) return false;
   const size_t nb = idat.size() - 2;
   if (nb != ((size_t)h + band_rows - 1) / band_rows) return false;
-  const size_t ch = ctype == 6 ? 4 : 3, line = 1 + ch * (size_t)w;
+  const size_t ch = ctype == 6 ? 4 : 3, line = 1 + ch * (size_t)(depth / 8) * (size_t)w;
   if (std::min<size_t>(band_rows, h) * line > ((size_t)1 << 30)) return false;
   for (size_t i = 1; i + 1 < idat.size(); ++i)
     if (idat[i].second >= ((size_t)1 << 28)) return false;
   info.w = (int)w; info.h = (int)h; info.channels = (int)ch; info.band_rows = (int)band_rows; info.nbands = (int)nb;
+  info.depth = depth;
   info.bands.assign(idat.begin() + 1, idat.end() - 1);
   info.adler = be32(file + idat.back().first);
   return true;
 }
+}  // namespace
 
 void png_decode_run(hipStream_t st, PngDecodeBufs& D, const std::vector<const uint8_t*>& files, const std::vector<PngBandedInfo>& info,
                     const std::vector<uint8_t*>& dst, unsigned long long* stats, Profiler* prof) {
+  std::vector<PngDecodeDst> d(dst.size());
+  for (size_t i = 0; i < dst.size(); ++i) d[i].p = dst[i];
+  png_decode_run(st, D, files, info, d, {}, stats, prof);
+}
+void png_decode_run(hipStream_t st, PngDecodeBufs& D, const std::vector<const uint8_t*>& files, const std::vector<PngBandedInfo>& info,
+                    const std::vector<PngDecodeDst>& dst, const std::vector<hipEvent_t>& before, unsigned long long* stats, Profiler* prof) {
   const size_t nimg = info.size();
   if (!nimg) return;
   // where every file, every band's scanlines and the tables lie
@@ -689,13 +774,19 @@ void png_decode_run(hipStream_t st, PngDecodeBufs& D, const std::vector<const ui
   size_t in_bytes = 0, filt_bytes = 0;
   for (size_t i = 0; i < nimg; ++i) {
     const PngBandedInfo& P = info[i];
-    if (P.channels == 4 && (reinterpret_cast<uintptr_t>(dst[i]) & 3)) throw Error(S360_ERR_INVALID_ARG, "png decode: image not 4-byte aligned");
+    const PngDecodeDst& T = dst[i];
+    const int pix = P.channels * (P.depth / 8);
+    const bool slot = T.store == kPngStoreSide || T.store == kPngStorePole;
+    if (!(T.store == kPngStoreBytes || (T.store == kPngStoreU16 && P.depth == 16) || (slot && P.channels == 3)) || (pix != 3 && pix != 4 && pix != 6))
+      throw Error(S360_ERR_INVALID_ARG, "png decode: image " + std::to_string(i) + ": no such store for this file");
+    if ((P.channels == 4 || slot) && (reinterpret_cast<uintptr_t>(T.p) & 3)) throw Error(S360_ERR_INVALID_ARG, "png decode: image not 4-byte aligned");
+    if (T.store == kPngStoreU16 && (reinterpret_cast<uintptr_t>(T.p) & 1)) throw Error(S360_ERR_INVALID_ARG, "png decode: image not 2-byte aligned");
     size_t end = 0;
     for (const auto& b : P.bands) end = std::max(end, b.first + b.second);
     file_off[i] = in_bytes;
     in_bytes += (end + 15) & ~(size_t)15;
-    const unsigned line = 1u + (unsigned)P.channels * (unsigned)P.w;
-    imgs[i] = DecImage{dst[i], P.w, P.h, P.channels, line};
+    const unsigned line = 1u + (unsigned)pix * (unsigned)P.w;
+    imgs[i] = DecImage{T.p, P.w, P.h, pix, line, T.store, T.feather};
     for (int b = 0; b < P.nbands; ++b) {
       const int y0 = b * P.band_rows, rows = std::min(P.band_rows, P.h - y0);
       DecBand R;
@@ -739,6 +830,8 @@ void png_decode_run(hipStream_t st, PngDecodeBufs& D, const std::vector<const ui
     ProfScope ps(pr, "png_inflate");
     hipLaunchKernelGGL(k_png_inflate, dim3((unsigned)nb), dim3(64), 0, st, (const uint8_t*)din, dbands, D.filt.as<uint8_t>(), douts, dstats);
   }
+  for (hipEvent_t e : before)
+    if (e) S360_HIP(hipStreamWaitEvent(st, e, 0));
   {
     ProfScope ps(pr, "png_unfilter");
     hipLaunchKernelGGL(k_png_unfilter, dim3((unsigned)nb), dim3(kUT), 0, st, (const uint8_t*)D.filt.as<uint8_t>(), dbands, dimgs, douts);

@@ -15,6 +15,7 @@ namespace s360 {
 // What the host reads out of the container of a file this decoder takes (png_parse_banded).
 struct PngBandedInfo {
   int w = 0, h = 0, channels = 0, band_rows = 0, nbands = 0;
+  int depth = 8;                                 // bits per sample: 8, or (png_parse_banded_input only) 16 with 3 channels
   std::vector<std::pair<size_t, size_t>> bands;  // (offset, length) of every band's IDAT data in the file
   uint32_t adler = 0;                            // the file's trailing Adler-32 (of all filtered scanlines)
 };
@@ -23,6 +24,22 @@ struct PngBandedInfo {
 // like this function, does not check the chunks' CRCs), and every band is small enough for 32-bit bit positions (rows x line <=
 // 2^30 bytes, segment < 2^28 bytes). false: not this decoder's file; `info` is untouched.
 bool png_parse_banded(const uint8_t* file, size_t n, PngBandedInfo& info);
+// ... and the camera-image form (include/s360_input_png.h): the same, plus depth 16 with colour type 2 — what png.hip's k_png_band<6>
+// writes: 6 bytes per pixel, R,G,B with the high byte first, line = 1 + 6 w, the same two bounds.
+bool png_parse_banded_input(const uint8_t* file, size_t n, PngBandedInfo& info);
+
+// Where k_png_unfilter leaves an image's pixels.
+enum PngStore : int {
+  kPngStoreBytes = 0,  // packed 8-bit B,G,R(,A); a 16-bit file keeps its samples' high bytes (png_set_strip_16)
+  kPngStoreU16 = 1,    // packed little-endian uint16 B,G,R: 16-bit files only, 2-byte aligned
+  kPngStoreSide = 2,   // a side camera's source slot: uchar4 B,G,R,A with side_src_alpha's row ramp (3-channel files)
+  kPngStorePole = 3    // a pole camera's source slot: uchar4 B,G,R,255 (3-channel files)
+};
+struct PngDecodeDst {
+  uint8_t* p = nullptr;  // device memory
+  int store = kPngStoreBytes;
+  int feather = 0;       // kPngStoreSide: side_alpha_feather_size
+};
 
 // What png_decode_run throws: the first image whose bands failed (include/s360_png_decode.h: S360_PNG_DECODE_FAILURE_DAMAGED).
 struct PngDecodeError : Error {
@@ -41,5 +58,9 @@ constexpr int kPngDecodeStatWords = 4 + 66;  // fast, general, stored-only, most
 // kPngDecodeStatWords counters of this call; `prof` (may be null) the two kernels' times as "png_inflate" and "png_unfilter".
 void png_decode_run(hipStream_t st, PngDecodeBufs& D, const std::vector<const uint8_t*>& files, const std::vector<PngBandedInfo>& info,
                     const std::vector<uint8_t*>& dst, unsigned long long* stats, Profiler* prof);
+// The same with a store per image (8- and 16-bit files); the stream waits for the events of `before` (null entries are skipped) in
+// front of the unfilter launch, the first kernel that writes the destinations.
+void png_decode_run(hipStream_t st, PngDecodeBufs& D, const std::vector<const uint8_t*>& files, const std::vector<PngBandedInfo>& info,
+                    const std::vector<PngDecodeDst>& dst, const std::vector<hipEvent_t>& before, unsigned long long* stats, Profiler* prof);
 
 }  // namespace s360

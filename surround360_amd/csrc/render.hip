@@ -362,6 +362,54 @@ void frame_upload_raw(s360_ctx* c, s360_isp* isp, int which, const void* raw, in
   uploads_done(c);
 }
 
+// Camera images from their banded PNG files (include/s360_input_png.h): the files' bytes, one inflate launch and one unfilter
+// launch on the upload stream; the unfilter kernel writes the source slots itself (side: the alpha ramp of launch_prepare_side_src,
+// pole: alpha 255) behind the previous frame's projections. The caller (api_png.hip) has checked cameras, channels and sizes.
+// Synchronous (png_decode_run waits for the status words); throws PngDecodeError with nothing marked.
+void frame_upload_png(s360_ctx* c, const std::vector<int>& cams, const std::vector<const uint8_t*>& files,
+                      const std::vector<PngBandedInfo>& info) {
+  FrameState& F = frame_state(c);
+  ensure_upload_stream(c);
+  bool side = false, pole = false;
+  for (size_t i = 0; i < cams.size(); ++i) {
+    if (cams[i] < 0) { pole = true; continue; }
+    if (!side) F.sideSrc.ensure((size_t)F.P * info[i].w * info[i].h * sizeof(uchar4));
+    side = true;
+  }
+  std::vector<PngDecodeDst> dst(cams.size());
+  for (size_t i = 0; i < cams.size(); ++i) {
+    const size_t n = (size_t)info[i].w * info[i].h;
+    if (cams[i] >= 0) {
+      dst[i].p = reinterpret_cast<uint8_t*>(F.sideSrc.as<uchar4>() + n * cams[i]);
+      dst[i].store = kPngStoreSide;
+      dst[i].feather = c->P.side_alpha_feather_size;
+    } else {
+      DevBuf& d = cams[i] == S360_CAMERA_TOP ? F.topSrc : F.botSrc;
+      d.ensure(n * sizeof(uchar4));
+      dst[i].p = d.as<uint8_t>();
+      dst[i].store = kPngStorePole;
+    }
+  }
+  const std::vector<hipEvent_t> before = {side && c->haveSideSrcFree ? c->evSideSrcFree : nullptr,
+                                          pole && c->havePoleSrcFree ? c->evPoleSrcFree : nullptr};
+  png_decode_run(c->stUp, c->pngDec, files, info, dst, before, c->pngDecStats, nullptr);
+  for (size_t i = 0; i < cams.size(); ++i) {
+    if (cams[i] >= 0) {
+      F.srcW = info[i].w;
+      F.srcH = info[i].h;
+      F.have_side = true;
+      F.side_uploaded |= 1ull << cams[i];
+    } else if (cams[i] == S360_CAMERA_TOP) {
+      F.topW = info[i].w; F.topH = info[i].h;
+      F.have_top = true;
+    } else {
+      F.poleW = info[i].w; F.poleH = info[i].h;
+      F.have_bottom = true;
+    }
+  }
+  uploads_done(c);
+}
+
 void frame_upload_pole_removal(s360_ctx* c, const uint8_t* bottom2, const uint8_t* mask, const uint8_t* mask2, int w, int h) {
   FrameState& F = frame_state(c);
   if (F.have_bottom && (w != F.poleW || h != F.poleH))

@@ -162,6 +162,9 @@ void frame_upload_side(s360_ctx* c, int idx, const uint8_t* img, int w, int h, i
 void frame_upload_pole(s360_ctx* c, bool top, const uint8_t* bgr, int w, int h);
 void frame_upload_raw(s360_ctx* c, struct s360_isp* isp, int which, const void* raw, int bits, int inW, int inH);
 void frame_upload_pole_removal(s360_ctx* c, const uint8_t* bottom2, const uint8_t* mask, const uint8_t* mask2, int w, int h);
+// cams[i]: side index, S360_CAMERA_TOP or S360_CAMERA_BOTTOM; info[i]: files[i] parsed (png_parse_banded_input), 3 channels
+void frame_upload_png(s360_ctx* c, const std::vector<int>& cams, const std::vector<const uint8_t*>& files,
+                      const std::vector<PngBandedInfo>& info);
 void frame_render_pairs(s360_ctx* c, int p0, int p1, int use_prev);
 void frame_finish(s360_ctx* c, int pole_mask, int use_prev);
 // the two halves of frame_finish for a frame whose pole units are spread over GPUs

@@ -32,13 +32,7 @@ __global__ __launch_bounds__(256) void k_prepare_side_src(const uint8_t* __restr
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= w) return;
   const uint8_t* p = src + ((size_t)y * w + x) * cn;
-  int a = cn == 4 ? p[3] : 255;
-  // rows [0,feather) and [h-feather,h): alpha = uint8(255.0f * float(yy + 0.5f) / float(feather)), yy being
-  // the loop iteration of TRSP:117-124 that touches this row.
-  int yy = -1;
-  if (y < feather) yy = y;
-  if (h - 1 - y < feather) yy = max(yy, h - 1 - y);  // the later loop iteration wins
-  if (yy >= 0) a = (int)(unsigned char)(255.0f * (float)(yy + 0.5f) / (float)feather);
+  const int a = side_src_alpha(y, h, feather, cn == 4 ? p[3] : 255);
   dst[(size_t)y * w + x] = make_uchar4(p[0], p[1], p[2], (unsigned char)a);
 }
 

@@ -35,6 +35,17 @@ struct PoleWarpParams {  // TRSP:483-536
   float poleCameraRadius, phiRampStart, phiMid, phiRampEnd;
 };
 
+// The alpha of row y of a side camera's source image of h rows (projectSideToSpherical's source-row ramp, TRSP:108-125): rows
+// [0,feather) and [h-feather,h) get uint8(255.0f * float(yy + 0.5f) / float(feather)), yy being the loop iteration of TRSP:117-124
+// that touches this row; every other row keeps `a`. Shared by k_prepare_side_src and the PNG decoder's side-slot store.
+__host__ __device__ inline int side_src_alpha(int y, int h, int feather, int a) {
+  int yy = -1;
+  if (y < feather) yy = y;
+  if (h - 1 - y < feather) yy = yy > h - 1 - y ? yy : h - 1 - y;  // the later loop iteration wins
+  if (yy >= 0) a = (int)(unsigned char)(255.0f * (float)(yy + 0.5f) / (float)feather);
+  return a;
+}
+
 // generic
 void launch_bgr_to_bgra(hipStream_t st, const uint8_t* src, int channels, uchar4* dst, size_t n);
 void launch_u16_high_byte(hipStream_t st, const unsigned short* src, uint8_t* dst, size_t n);

@@ -731,6 +731,45 @@ class Context:
             self.h, k, names, (C.c_int * k)(*[int(i) for _, i in names_idx]), (C.c_void_p * k)(*[b.ctypes.data for b in bufs]),
             (C.c_size_t * k)(*[b.size for b in bufs])))
 
+    def decode_input_png_batch(self, files, keep16=False, caps=None, outs=None):
+        """s360_decode_input_png_batch: a list of banded PNG files (bytes), 8-bit or 16-bit RGB, -> the list of their images decoded
+        by one launch sequence on the device: (h, w, c) uint8 B,G,R(,A); a 16-bit file gives (h, w, 3) uint16 B,G,R if `keep16`, else
+        its samples' high bytes as uint8. `caps`: output buffer sizes in bytes to offer instead of the images' own (a smaller one is
+        refused); `outs`: uint8 buffers to decode into (default: new ones of those sizes)."""
+        k = len(files)
+        assert k > 0
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        sizes = []
+        for f in bufs:
+            d = input_png_decodable(f)
+            sizes.append(d[0] * d[1] * d[2] * (2 if d[3] == 16 and keep16 else 1) if d else 0)
+        if caps is not None:
+            sizes = [int(v) for v in caps]
+        if outs is None:
+            outs = [np.empty(max(n + (n & 1), 2), np.uint8) for n in sizes]
+        got = (C.c_int * (5 * k))()
+        self._ck(lib().s360_decode_input_png_batch(
+            self.h, k, (C.c_void_p * k)(*[b.ctypes.data for b in bufs]), (C.c_size_t * k)(*[b.size for b in bufs]),
+            (C.c_void_p * k)(*[o.ctypes.data for o in outs]), (C.c_size_t * k)(*sizes), 1 if keep16 else 0, got))
+        res = []
+        for i, o in enumerate(outs):
+            w, h, c, depth = got[5 * i:5 * i + 4]
+            if depth == 16 and keep16:
+                res.append(o[:w * h * c * 2].view(np.uint16).reshape(h, w, c))
+            else:
+                res.append(o[:w * h * c].reshape(h, w, c))
+        return res
+
+    def upload_frame_png(self, cameras, files):
+        """s360_frame_upload_png: camera images from their banded PNG files (bytes; colour type 2, 8- or 16-bit), decoded on the
+        device straight into the frame's source slots. cameras: side indices, -1 (top), -2 (bottom). Synchronous."""
+        k = len(cameras)
+        assert k == len(files) and k > 0
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        self._ck(lib().s360_frame_upload_png(
+            self.h, k, (C.c_int * k)(*[int(v) for v in cameras]), (C.c_void_p * k)(*[b.ctypes.data if b.size else None for b in bufs]),
+            (C.c_size_t * k)(*[b.size for b in bufs])))
+
     def set_prev_flow(self, name, idx, flow):
         """s360_frame_set_prev_flow: one previous-frame flow (the names of get_f32) as (h, w, 2) float32."""
         flow = np.ascontiguousarray(flow, np.float32)
@@ -914,3 +953,13 @@ def png_decodable(file):
     if lib().s360_png_decodable(b.ctypes.data if b.size else None, C.c_size_t(b.size), whc, C.byref(rows)) != 0:
         return None
     return whc[0], whc[1], whc[2], rows.value
+
+
+def input_png_decodable(file):
+    """s360_input_png_decodable (host only): (w, h, channels, bits per sample, band_rows) if `file` (bytes) is a banded PNG the
+    camera-image decoder takes (what png_decodable takes, or 16-bit RGB), else None."""
+    b = np.frombuffer(bytes(file), np.uint8) if not isinstance(file, np.ndarray) else file
+    info = (C.c_int * 5)()
+    if lib().s360_input_png_decodable(b.ctypes.data if b.size else None, C.c_size_t(b.size), info) != 0:
+        return None
+    return tuple(info)

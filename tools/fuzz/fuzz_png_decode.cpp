@@ -1,6 +1,8 @@
 // feeds the files of a directory to the device PNG decoder of the emulated, sanitised library (s360_png_decodable,
 // s360_decode_png_batch), every file on a fresh context and with output buffers of exactly the image's size; writes <file>.out (the pixels) where the library reports
-// success, and one line per file: "<name> <return code>". argv: rig.json dir
+// success, and one line per file: "<name> <return code>". A 16-bit file (s360_input_png_decodable takes it, s360_png_decodable does
+// not) goes through s360_decode_input_png_batch twice, to uint16 samples (<file>.out) and to high bytes (<file>.out8), again with
+// buffers of exactly those sizes. argv: rig.json dir
 #include <dirent.h>
 #include <cstdio>
 #include <cstring>
@@ -50,6 +52,23 @@ int main(int argc, char** argv) {
       if (rc == S360_OK) { std::ofstream o(path + ".out", std::ios::binary); o.write((const char*)out, (std::streamsize)bytes); }
       delete[] out;
       s360_destroy(c);
+    }
+    int info[5] = {0, 0, 0, 0, 0};
+    if (rc != S360_OK && s360_input_png_decodable(file, src.size(), info) == S360_OK && info[3] == 16) {
+      for (int keep16 = 1; keep16 >= 0; --keep16) {
+        s360_ctx* c = nullptr;
+        if (s360_create(&c, 0, cams.data(), n, &P) != S360_OK) { std::fprintf(stderr, "create: %s\n", s360_last_error(nullptr)); return 2; }
+        const size_t bytes = (size_t)info[0] * info[1] * info[2] * (keep16 ? 2 : 1);
+        uint8_t* out = new uint8_t[bytes];  // (operator new: aligned for uint16)
+        const uint8_t* files[1] = {file};
+        const size_t len[1] = {src.size()}, cap[1] = {bytes};
+        void* outs[1] = {out};
+        rc = s360_decode_input_png_batch(c, 1, files, len, outs, cap, keep16, nullptr);
+        if (rc == S360_OK) { std::ofstream o(path + (keep16 ? ".out" : ".out8"), std::ios::binary); o.write((const char*)out, (std::streamsize)bytes); }
+        delete[] out;
+        s360_destroy(c);
+        if (rc != S360_OK) break;
+      }
     }
     delete[] file;
     std::printf("%s %d\n", nm.c_str(), rc);
