@@ -28,6 +28,7 @@
 #include <map>
 #include <memory>
 #include <sstream>
+#include <set>
 #include <string>
 #include <thread>
 #include <vector>
@@ -78,6 +79,13 @@ struct Flags {
          // and their pixels being uploaded. Every other file (cv::imwrite's, RGBA, JPEG, interlaced) takes the host decoder and
          // the pixel upload as before, file by file. Same files written either way. Ignored with --bin_list.
          {"device_input_png", "false"},
+         // --device_input_jpeg (default off; S360_DEVICE_INPUT_JPEG=1 in the environment switches it on, a flag on the command line
+         // wins over the environment): the same for camera images that are baseline JPEG files — what a .jpg imgs_dir holds. The
+         // files s360_input_jpeg_decodable takes (8-bit YCbCr, 4:2:0 / 4:2:2 / 4:4:4, one scan, no restart markers) go to every GPU
+         // context that needs them in ONE s360_frame_upload_jpeg; every other file (greyscale, restart markers, PNG)
+         // takes the host decoder and the pixel upload as before, file by file. May be combined with --device_input_png: a
+         // directory may hold either kind. Same files written either way. Ignored with --bin_list.
+         {"device_input_jpeg", "false"},
          // --num_gpus G: the 14 side pairs of the frame sharded over G GPUs, one RCCL strip gather
          {"num_gpus", "1"},
          // --num_frames N: frames frame_number .. +N-1 as ONE stream in this process (temporal state stays on the
@@ -104,7 +112,7 @@ struct Flags {
   static bool is_bool(const std::string& k) {
     static const char* b[] = {"save_debug_images", "enable_top", "enable_bottom", "enable_pole_removal", "logtostderr",
                               "alsologtostderr", "write_state", "soft_isp", "device_png", "device_state_png", "device_state_read",
-                              "device_input_png"};
+                              "device_input_png", "device_input_jpeg"};
     for (auto s : b)
       if (k == s) return true;
     return false;
@@ -121,7 +129,11 @@ struct Flags {
       if (eq != std::string::npos) { key = a.substr(0, eq); val = a.substr(eq + 1); has = true; }
       if (key == "help") { usage(); std::exit(0); }
       if (!v.count(key)) {
-        if (key.rfind("no", 0) == 0 && v.count(key.substr(2)) && is_bool(key.substr(2)) && !has) { v[key.substr(2)] = "false"; continue; }
+        if (key.rfind("no", 0) == 0 && v.count(key.substr(2)) && is_bool(key.substr(2)) && !has) {
+          v[key.substr(2)] = "false";
+          given.insert(key.substr(2));
+          continue;
+        }
         fail("unknown command line flag '" + key + "'");
       }
       if (!has) {
@@ -137,8 +149,10 @@ struct Flags {
         }
       }
       v[key] = val;
+      given.insert(key);
     }
   }
+  std::set<std::string> given;  // the flags the command line named
   std::string s(const std::string& k) const { return v.at(k); }
   double d(const std::string& k) const { return std::atof(v.at(k).c_str()); }
   int i(const std::string& k) const { return std::atoi(v.at(k).c_str()); }
@@ -284,23 +298,44 @@ void assign_pole_units(Job& J) {
   J.need[0] = 3;  // the root composites both eyes
 }
 
-// --device_input_png: how many camera files took which path (--v 1)
-std::atomic<int> g_inputOnDevice(0), g_inputOnHost(0);
+// --device_input_png / --device_input_jpeg: how many camera files took which path (--v 1)
+std::atomic<int> g_inputOnDevice(0), g_inputJpegOnDevice(0), g_inputOnHost(0);
 bool device_input_png(const Flags& F) {
   const char* e = std::getenv("S360_DEVICE_INPUT_PNG");
   return F.s("bin_list").empty() && (F.b("device_input_png") || (e && !std::strcmp(e, "1")));
 }
+bool device_input_jpeg(const Flags& F) {
+  if (!F.s("bin_list").empty()) return false;
+  if (F.given.count("device_input_jpeg")) return F.b("device_input_jpeg");
+  const char* e = std::getenv("S360_DEVICE_INPUT_JPEG");
+  return e && !std::strcmp(e, "1");
+}
+// --v 1: one line for the camera files, whichever of the two flags are on (the host count is of the files neither decoder took)
+void report_input_paths(const Flags& F) {
+  const bool p = device_input_png(F), j = device_input_jpeg(F);
+  if (!p && !j) return;
+  std::fprintf(stderr, "camera images:           %d files decoded on the device, %d on the host (%s)\n",
+               (p ? g_inputOnDevice.load() : 0) + (j ? g_inputJpegOnDevice.load() : 0), g_inputOnHost.load(),
+               p && j ? "--device_input_png --device_input_jpeg" : p ? "--device_input_png" : "--device_input_jpeg");
+}
+// which of the two a kept file is: JPEG files begin with SOI
+bool is_jpeg_file(const std::vector<uint8_t>& f) { return f.size() >= 2 && f[0] == 0xFF && f[1] == 0xD8; }
 std::vector<uint8_t> read_bytes(const std::string& path);
-// One camera's image: with --device_input_png its file's bytes if the device decoder takes them as a 3-channel image (`file`
-// keeps them, `im` gets the size only), else the pixels as the host decodes them.
-void load_camera_image(bool device, const std::string& path, pngio::Image& im, std::vector<uint8_t>& file) {
+// One camera's image: with --device_input_png / --device_input_jpeg its file's bytes if that device decoder takes them as a
+// 3-channel image (`file` keeps them, `im` gets the size only), else the pixels as the host decodes them.
+void load_camera_image(bool devicePng, bool deviceJpeg, const std::string& path, pngio::Image& im, std::vector<uint8_t>& file) {
   file.clear();
-  if (device) {
+  if (devicePng || deviceJpeg) {
     file = read_bytes(path);
-    int info[5] = {0, 0, 0, 0, 0};
-    if (s360_input_png_decodable(file.data(), file.size(), info) == S360_OK && info[2] == 3) {
+    int info[6] = {0, 0, 0, 0, 0, 0};
+    if (devicePng && s360_input_png_decodable(file.data(), file.size(), info) == S360_OK && info[2] == 3) {
       im.w = info[0]; im.h = info[1]; im.c = 3;  // (the size is known, e.g. to the pole-removal check; no pixels on the host)
       ++g_inputOnDevice;
+      return;
+    }
+    if (deviceJpeg && s360_input_jpeg_decodable(file.data(), file.size(), info) == S360_OK) {
+      im.w = info[0]; im.h = info[1]; im.c = 3;
+      ++g_inputJpegOnDevice;
       return;
     }
     file.clear();
@@ -321,17 +356,17 @@ FrameInputs load_frame(const Job& J, const std::string& frame, FrameInputs recyc
   }
   in.side.resize(J.P);
   in.sideFile.resize(J.P);
-  const bool dev = device_input_png(J.F);
+  const bool dev = device_input_png(J.F), devJ = device_input_jpeg(J.F);
   const std::string imgs = J.F.s("imgs_dir");
   std::vector<std::thread> th;
   for (int k = 0; k < J.P; ++k)
     th.emplace_back([&, k] {
       const std::string dir = imgs + "/" + J.cams[J.sideIdx[k]].id;
-      load_camera_image(dev, dir + "/" + frame + image_extension(dir), in.side[k], in.sideFile[k]);
+      load_camera_image(dev, devJ, dir + "/" + frame + image_extension(dir), in.side[k], in.sideFile[k]);
     });
-  if (J.prm.enable_top) th.emplace_back([&] { load_camera_image(dev, imgs + "/" + J.cams[J.ti].id + "/" + frame + ".png", in.top, in.topFile); });  // TRSP:652
+  if (J.prm.enable_top) th.emplace_back([&] { load_camera_image(dev, devJ, imgs + "/" + J.cams[J.ti].id + "/" + frame + ".png", in.top, in.topFile); });  // TRSP:652
   if (J.prm.enable_bottom) {
-    th.emplace_back([&] { load_camera_image(dev, imgs + "/" + J.cams[J.bi].id + "/" + frame + ".png", in.bottom, in.bottomFile); });  // TRSP:602
+    th.emplace_back([&] { load_camera_image(dev, devJ, imgs + "/" + J.cams[J.bi].id + "/" + frame + ".png", in.bottom, in.bottomFile); });  // TRSP:602
     if (J.prm.enable_pole_removal) {  // PoleRemoval.cpp:48-66
       const std::string masks = J.F.s("bottom_pole_masks_dir");
       th.emplace_back([&] { in.bottom2 = load_png(imgs + "/" + J.cams[J.b2].id + "/" + frame + ".png", false); });
@@ -371,14 +406,15 @@ void upload_frame(const Job& J, const FrameInputs& in) {
   for (int r = 0; r < G; ++r) {
     std::vector<char> need(J.P, 0);
     for (int p = J.bounds[r]; p < J.bounds[r + 1]; ++p) need[p] = need[(p + 1) % J.P] = 1;
-    // --device_input_png: the cameras of this GPU whose files the device decodes, in one call (synchronous; a damaged file dies
-    // here like a file the host decoder cannot read)
-    std::vector<int> cams;
-    std::vector<const uint8_t*> files;
-    std::vector<size_t> bytes;
+    // --device_input_png / --device_input_jpeg: the cameras of this GPU whose files the device decodes, in one call per kind
+    // (synchronous; a damaged file dies here like a file the host decoder cannot read)
+    std::vector<int> cams, camsJ;
+    std::vector<const uint8_t*> files, filesJ;
+    std::vector<size_t> bytes, bytesJ;
     auto by_file = [&](int camera, const std::vector<uint8_t>& f) {
       if (f.empty()) return false;
-      cams.push_back(camera); files.push_back(f.data()); bytes.push_back(f.size());
+      const bool j = is_jpeg_file(f);
+      (j ? camsJ : cams).push_back(camera); (j ? filesJ : files).push_back(f.data()); (j ? bytesJ : bytes).push_back(f.size());
       return true;
     };
     for (int k = 0; k < J.P; ++k)
@@ -387,6 +423,7 @@ void upload_frame(const Job& J, const FrameInputs& in) {
     if (J.unitMask[r] & 3) by_file(S360_CAMERA_TOP, in.topFile);
     if (J.unitMask[r] & 12) by_file(S360_CAMERA_BOTTOM, in.bottomFile);
     if (!cams.empty()) ck(s360_frame_upload_png(J.ctx[r], (int)cams.size(), cams.data(), files.data(), bytes.data()), J.ctx[r]);
+    if (!camsJ.empty()) ck(s360_frame_upload_jpeg(J.ctx[r], (int)camsJ.size(), camsJ.data(), filesJ.data(), bytesJ.data()), J.ctx[r]);
   }
   for (int r = 0; r < G; ++r) {  // the pole images go to the GPUs that run units of that pole
     s360_ctx* c = J.ctx[r];
@@ -1243,9 +1280,7 @@ static int run_job(const Flags& flags) {
                    tDecode / nf, tUpload / nf, tFetch / nf, tJoin / nf, per - (tDecode + tUpload + tFetch + tJoin) / nf, per,
                    numFrames - nf, numFrames - 1);
     }
-    if (device_input_png(F))
-      std::fprintf(stderr, "camera images:           %d files decoded on the device, %d on the host (--device_input_png)\n", g_inputOnDevice.load(),
-                   g_inputOnHost.load());
+    report_input_paths(F);
     std::fprintf(stderr, "TOTAL:                   %.3f\n", endTime - startTime);
   }
   if (g_fast_exit) return 0;  // main leaves the process at once (one frame per process): the device memory goes with it
@@ -1459,9 +1494,7 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
     if (later > 0 && endTime > tStep0)
       std::fprintf(stderr, "steady state:            %d frames of steps 1..%d in %.3f  (%.2f frames per second, files written)\n", later, steps - 1,
                    endTime - tStep0, later / (endTime - tStep0));
-    if (device_input_png(flags))
-      std::fprintf(stderr, "camera images:           %d files decoded on the device, %d on the host (--device_input_png)\n", g_inputOnDevice.load(),
-                   g_inputOnHost.load());
+    report_input_paths(flags);
     std::fprintf(stderr, "TOTAL:                   %.3f\n", endTime - startTime);
   }
   for (auto& kv : J.binCam)

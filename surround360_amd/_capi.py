@@ -106,6 +106,11 @@ ISP_PNG_SYMBOLS = [
 ]
 # ... and every symbol include/s360_input_png.h declares (camera images as banded PNG files, 8- or 16-bit, decoded on the device)
 INPUT_PNG_SYMBOLS = ("s360_input_png_decodable", "s360_decode_input_png_batch", "s360_frame_upload_png")
+# ... and every symbol include/s360_input_jpeg.h declares (camera images as baseline JPEG files decoded on the device)
+INPUT_JPEG_SYMBOLS = ("s360_input_jpeg_decodable", "s360_decode_input_jpeg_batch", "s360_frame_upload_jpeg", "s360_jpeg_decode_stats",
+                      "s360_jpeg_decode_failure")
+# ... and its test tap, include/s360_debug_input_jpeg.h
+DEBUG_INPUT_JPEG_SYMBOLS = ("s360_debug_input_jpeg_blocks",)
 # ... and the test taps include/s360_debug.h declares (not part of the API)
 DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
 # ... and the one include/s360_debug_final_flow.h declares
@@ -224,6 +229,19 @@ def lib():
                                                   C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int)]
         L.s360_frame_upload_png.restype = C.c_int
         L.s360_frame_upload_png.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.s360_input_jpeg_decodable.restype = C.c_int
+        L.s360_input_jpeg_decodable.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
+        L.s360_decode_input_jpeg_batch.restype = C.c_int
+        L.s360_decode_input_jpeg_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+        L.s360_frame_upload_jpeg.restype = C.c_int
+        L.s360_frame_upload_jpeg.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.s360_jpeg_decode_stats.restype = C.c_int
+        L.s360_jpeg_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int]
+        L.s360_jpeg_decode_failure.restype = C.c_int
+        L.s360_jpeg_decode_failure.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.s360_debug_input_jpeg_blocks.restype = C.c_int
+        L.s360_debug_input_jpeg_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.s360_debug_isp_stages.restype = C.c_int
         L.s360_debug_isp_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8
         L.s360_debug_flow_level.restype = C.c_int

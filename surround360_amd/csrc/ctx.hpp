@@ -8,6 +8,7 @@
 #include "core.hpp"
 #include "flow.hpp"
 #include "png.hpp"
+#include "jpeg_decode.hpp"
 #include "png_decode.hpp"
 #include "rig.hpp"
 
@@ -64,6 +65,10 @@ struct s360_ctx {
   s360::PngDecodeBufs pngDec;
   unsigned long long pngDecStats[s360::kPngDecodeStatWords] = {0};
   int pngDecFailImage = -1, pngDecFailReason = 0;  // s360_png_decode_failure: of the last decode call
+  // the JPEG decoder (jpeg_decode.hip): its buffers (grow only), the counters and the failure of the last decode call on this context
+  s360::JpegDecodeBufs jpegDec;
+  s360::JpegDecodeStats jpegDecStats;
+  int jpegDecFailImage = -1, jpegDecFailReason = 0;
   hipEvent_t evUpHost = nullptr; // s360_frame_uploads_complete
   static constexpr int kPinChunks = 4;
   static constexpr size_t kPinChunkBytes = (size_t)8 << 20;

@@ -410,6 +410,52 @@ void frame_upload_png(s360_ctx* c, const std::vector<int>& cams, const std::vect
   uploads_done(c);
 }
 
+// The same from baseline JPEG files (include/s360_input_jpeg.h): the scans' bytes and the decoder's launches on the upload stream;
+// k_jpeg_pixels writes the source slots behind the previous frame's projections. Synchronous; throws JpegDecodeError with nothing marked.
+void frame_upload_jpeg(s360_ctx* c, const std::vector<int>& cams, const std::vector<const uint8_t*>& files,
+                       const std::vector<JpegInInfo>& info) {
+  FrameState& F = frame_state(c);
+  ensure_upload_stream(c);
+  bool side = false, pole = false;
+  for (size_t i = 0; i < cams.size(); ++i) {
+    if (cams[i] < 0) { pole = true; continue; }
+    if (!side) F.sideSrc.ensure((size_t)F.P * info[i].w * info[i].h * sizeof(uchar4));
+    side = true;
+  }
+  std::vector<JpegDecodeDst> dst(cams.size());
+  for (size_t i = 0; i < cams.size(); ++i) {
+    const size_t n = (size_t)info[i].w * info[i].h;
+    if (cams[i] >= 0) {
+      dst[i].p = reinterpret_cast<uint8_t*>(F.sideSrc.as<uchar4>() + n * cams[i]);
+      dst[i].store = kJpegStoreSide;
+      dst[i].feather = c->P.side_alpha_feather_size;
+    } else {
+      DevBuf& d = cams[i] == S360_CAMERA_TOP ? F.topSrc : F.botSrc;
+      d.ensure(n * sizeof(uchar4));
+      dst[i].p = d.as<uint8_t>();
+      dst[i].store = kJpegStorePole;
+    }
+  }
+  const std::vector<hipEvent_t> before = {side && c->haveSideSrcFree ? c->evSideSrcFree : nullptr,
+                                          pole && c->havePoleSrcFree ? c->evPoleSrcFree : nullptr};
+  jpeg_decode_run(c->stUp, c->jpegDec, files, info, dst, before, c->jpegDecStats);
+  for (size_t i = 0; i < cams.size(); ++i) {
+    if (cams[i] >= 0) {
+      F.srcW = info[i].w;
+      F.srcH = info[i].h;
+      F.have_side = true;
+      F.side_uploaded |= 1ull << cams[i];
+    } else if (cams[i] == S360_CAMERA_TOP) {
+      F.topW = info[i].w; F.topH = info[i].h;
+      F.have_top = true;
+    } else {
+      F.poleW = info[i].w; F.poleH = info[i].h;
+      F.have_bottom = true;
+    }
+  }
+  uploads_done(c);
+}
+
 void frame_upload_pole_removal(s360_ctx* c, const uint8_t* bottom2, const uint8_t* mask, const uint8_t* mask2, int w, int h) {
   FrameState& F = frame_state(c);
   if (F.have_bottom && (w != F.poleW || h != F.poleH))

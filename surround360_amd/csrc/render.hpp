@@ -165,6 +165,9 @@ void frame_upload_pole_removal(s360_ctx* c, const uint8_t* bottom2, const uint8_
 // cams[i]: side index, S360_CAMERA_TOP or S360_CAMERA_BOTTOM; info[i]: files[i] parsed (png_parse_banded_input), 3 channels
 void frame_upload_png(s360_ctx* c, const std::vector<int>& cams, const std::vector<const uint8_t*>& files,
                       const std::vector<PngBandedInfo>& info);
+// ... and the same from baseline JPEG files (include/s360_input_jpeg.h); info[i]: files[i] parsed (jpeg_in_parse)
+void frame_upload_jpeg(s360_ctx* c, const std::vector<int>& cams, const std::vector<const uint8_t*>& files,
+                       const std::vector<JpegInInfo>& info);
 void frame_render_pairs(s360_ctx* c, int p0, int p1, int use_prev);
 void frame_finish(s360_ctx* c, int pole_mask, int use_prev);
 // the two halves of frame_finish for a frame whose pole units are spread over GPUs

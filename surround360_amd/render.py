@@ -770,6 +770,68 @@ class Context:
             self.h, k, (C.c_int * k)(*[int(v) for v in cameras]), (C.c_void_p * k)(*[b.ctypes.data if b.size else None for b in bufs]),
             (C.c_size_t * k)(*[b.size for b in bufs])))
 
+    def decode_input_jpeg_batch(self, files, caps=None, outs=None):
+        """s360_decode_input_jpeg_batch: a list of baseline JPEG files (bytes) -> the list of their images, (h, w, 3) uint8 B,G,R,
+        decoded by one launch sequence on the device. `caps`: output buffer sizes in bytes to offer instead of the images' own (a
+        smaller one is refused); `outs`: uint8 buffers to decode into (default: new ones of those sizes)."""
+        k = len(files)
+        assert k > 0
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        sizes = []
+        for f in bufs:
+            d = input_jpeg_decodable(f)
+            sizes.append(d[0] * d[1] * 3 if d else 0)
+        if caps is not None:
+            sizes = [int(v) for v in caps]
+        if outs is None:
+            outs = [np.empty(max(n, 1), np.uint8) for n in sizes]
+        got = (C.c_int * (6 * k))()
+        self._ck(lib().s360_decode_input_jpeg_batch(
+            self.h, k, (C.c_void_p * k)(*[b.ctypes.data if b.size else None for b in bufs]), (C.c_size_t * k)(*[b.size for b in bufs]),
+            (C.c_void_p * k)(*[o.ctypes.data for o in outs]), (C.c_size_t * k)(*sizes), got))
+        return [o[:got[6 * i] * got[6 * i + 1] * 3].reshape(got[6 * i + 1], got[6 * i], 3) for i, o in enumerate(outs)]
+
+    def upload_jpeg(self, cameras, files):
+        """s360_frame_upload_jpeg: camera images from their baseline JPEG files (bytes), decoded on the device straight into the
+        frame's source slots. cameras: side indices, -1 (top), -2 (bottom). Synchronous."""
+        k = len(cameras)
+        assert k == len(files) and k > 0
+        bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+        self._ck(lib().s360_frame_upload_jpeg(
+            self.h, k, (C.c_int * k)(*[int(v) for v in cameras]), (C.c_void_p * k)(*[b.ctypes.data if b.size else None for b in bufs]),
+            (C.c_size_t * k)(*[b.size for b in bufs])))
+
+    def jpeg_decode_stats(self):
+        """s360_jpeg_decode_stats of the last JPEG decode call on this context: a dict with files, subsequences, rounds (the
+        synchronisation launches), most_file_rounds, ms_entropy, ms_pixels and file_rounds (a list, one entry per file)."""
+        counts, ms = (C.c_uint64 * 4)(), (C.c_double * 2)()
+        self._ck(lib().s360_jpeg_decode_stats(self.h, counts, ms, None, 0))
+        k = int(counts[0])
+        fr = (C.c_uint32 * max(k, 1))()
+        self._ck(lib().s360_jpeg_decode_stats(self.h, counts, ms, fr, k))
+        return {"files": k, "subsequences": int(counts[1]), "rounds": int(counts[2]), "most_file_rounds": int(counts[3]),
+                "ms_entropy": float(ms[0]), "ms_pixels": float(ms[1]), "file_rounds": [int(v) for v in fr[:k]]}
+
+    def jpeg_decode_failure(self):
+        """s360_jpeg_decode_failure: (image index or -1, reason) of the last JPEG decode call — reason 0 none, 1 not a file of this
+        decoder, 2 size / buffer mismatch, 3 invalid code, 4 run past 63, 5 scan ends short, 6 blocks missing, 7 bits left over, 8
+        marker inside the scan."""
+        image, reason = C.c_int(), C.c_int()
+        self._ck(lib().s360_jpeg_decode_failure(self.h, C.byref(image), C.byref(reason)))
+        return image.value, reason.value
+
+    def debug_input_jpeg_blocks(self, file):
+        """s360_debug_input_jpeg_blocks (test tap): the quantised coefficients the entropy stage left for `file`, (blocks, 64) int16 in
+        emission order, natural order inside a block, absolute DC, dummy blocks included."""
+        b = np.frombuffer(bytes(file), np.uint8)
+        d = input_jpeg_decodable(b)
+        n = (-(-d[0] // (8 * d[3]))) * (-(-d[1] // (8 * d[4]))) * (d[3] * d[4] + 2) if d else 1
+        out = np.zeros((n, 64), np.int16)
+        got = C.c_size_t()
+        self._ck(lib().s360_debug_input_jpeg_blocks(self.h, b.ctypes.data if b.size else None, C.c_size_t(b.size), out.ctypes.data, C.c_size_t(n),
+                                                    C.byref(got)))
+        return out[:got.value]
+
     def set_prev_flow(self, name, idx, flow):
         """s360_frame_set_prev_flow: one previous-frame flow (the names of get_f32) as (h, w, 2) float32."""
         flow = np.ascontiguousarray(flow, np.float32)
@@ -953,6 +1015,16 @@ def png_decodable(file):
     if lib().s360_png_decodable(b.ctypes.data if b.size else None, C.c_size_t(b.size), whc, C.byref(rows)) != 0:
         return None
     return whc[0], whc[1], whc[2], rows.value
+
+
+def input_jpeg_decodable(file):
+    """s360_input_jpeg_decodable (host only): (w, h, 3, luma h sampling, luma v sampling, scan bytes) if `file` (bytes) is a baseline
+    JPEG the device decoder takes, else None."""
+    b = np.frombuffer(bytes(file), np.uint8)
+    info = (C.c_int * 6)()
+    if lib().s360_input_jpeg_decodable(b.ctypes.data if b.size else None, C.c_size_t(b.size), info) != 0:
+        return None
+    return tuple(int(v) for v in info)
 
 
 def input_png_decodable(file):
