@@ -86,6 +86,14 @@ struct Flags {
          // takes the host decoder and the pixel upload as before, file by file. May be combined with --device_input_png: a
          // directory may hold either kind. Same files written either way. Ignored with --bin_list.
          {"device_input_jpeg", "false"},
+         // --device_jpeg (default off; S360_DEVICE_JPEG=1 in the environment switches it on, a flag on the command line wins over
+         // the environment): an --output_equirect_path / --output_cubemap_path that ends in .jpg, .jpeg or .jpe names a JPEG file, as
+         // it does for cv::imwrite. Without this flag host threads encode it (jpegio::encode, quality 95: the reference's way, a
+         // thread-second per 8K frame); with it the file is encoded on the GPU behind the frame's last kernel (s360_set_jpeg_encode /
+         // s360_frame_download_jpeg) and this program only writes the bytes. Same bytes in the file either way. Ignored for PNG
+         // outputs, whose switch is --device_png; the two may be combined when one output is .png and the other .jpg. The state
+         // images stay PNG files (they are read back with their alpha).
+         {"device_jpeg", "false"},
          // --num_gpus G: the 14 side pairs of the frame sharded over G GPUs, one RCCL strip gather
          {"num_gpus", "1"},
          // --num_frames N: frames frame_number .. +N-1 as ONE stream in this process (temporal state stays on the
@@ -112,7 +120,7 @@ struct Flags {
   static bool is_bool(const std::string& k) {
     static const char* b[] = {"save_debug_images", "enable_top", "enable_bottom", "enable_pole_removal", "logtostderr",
                               "alsologtostderr", "write_state", "soft_isp", "device_png", "device_state_png", "device_state_read",
-                              "device_input_png", "device_input_jpeg"};
+                              "device_input_png", "device_input_jpeg", "device_jpeg"};
     for (auto s : b)
       if (k == s) return true;
     return false;
@@ -239,6 +247,83 @@ void save_png(const std::string& path, const uint8_t* px, int w, int h, int c) {
   } catch (const std::exception& e) {
     die(e.what());
   }
+}
+
+// ---- the codec of an output file ----------------------------------------------------------------------------------------------
+// imwriteExceptionOnFail is cv::imwrite (CvUtil.h), and cv::imwrite chooses its encoder by the path's extension: .jpg, .jpeg and
+// .jpe (in either case) give a JPEG file at OpenCV's defaults — quality 95, 4:2:0: the file jpegio::encode writes — and everything
+// else this program writes stays a PNG. The equirect's path and the cubemap's decide independently. Each codec has a device
+// encoder behind a flag of its own (--device_png, --device_jpeg): with it the fetch returns the finished file and the writer
+// threads only write bytes; without it the pixels come back and the writer threads encode them.
+enum class OutMode { PngHost, PngDevice, JpegHost, JpegDevice };
+bool is_jpeg_path(const std::string& path) {
+  const size_t dot = path.rfind('.');
+  if (dot == std::string::npos || path.find('/', dot) != std::string::npos) return false;
+  std::string e = path.substr(dot);
+  for (char& ch : e) ch = (char)std::tolower((unsigned char)ch);
+  return e == ".jpg" || e == ".jpeg" || e == ".jpe";
+}
+bool device_jpeg(const Flags& F) {
+  if (F.given.count("device_jpeg")) return F.b("device_jpeg");
+  const char* e = std::getenv("S360_DEVICE_JPEG");
+  return e && !std::strcmp(e, "1");
+}
+OutMode out_mode(const Flags& F, const std::string& path) {
+  if (is_jpeg_path(path)) return device_jpeg(F) ? OutMode::JpegDevice : OutMode::JpegHost;
+  return F.b("device_png") ? OutMode::PngDevice : OutMode::PngHost;
+}
+bool is_file(OutMode m) { return m == OutMode::PngDevice || m == OutMode::JpegDevice; }  // the fetch returns the file, not pixels
+const char* mode_name(OutMode m) {
+  return m == OutMode::PngDevice ? "PNG encoded on the device" : m == OutMode::PngHost ? "PNG encoded on the host"
+       : m == OutMode::JpegDevice ? "JPEG encoded on the device" : "JPEG encoded on the host";
+}
+// --v 1: which path each output took
+void report_output_paths(OutMode eq, bool cube, OutMode cm) {
+  std::fprintf(stderr, "output files:            equirect %s", mode_name(eq));
+  if (cube) std::fprintf(stderr, ", cubemap %s", mode_name(cm));
+  std::fprintf(stderr, "\n");
+}
+// the device encoders the two outputs need, switched on for the frames rendered from now on
+void enable_output_encoders(s360_ctx* ctx, OutMode eq, bool cube, OutMode cm) {
+  const auto any = [&](OutMode m) { return eq == m || (cube && cm == m); };
+  if (any(OutMode::PngDevice)) ck(s360_set_png_encode(ctx, 1), ctx);
+  if (any(OutMode::JpegDevice)) ck(s360_set_jpeg_encode(ctx, 1, 95), ctx);
+}
+// what the buffer of an output must hold: the file's bound, or its w x h pixels
+size_t output_buffer_bytes(s360_ctx* ctx, OutMode m, bool cubemap, int w, int h) {
+  if (m == OutMode::PngDevice) return cubemap ? s360_frame_cubemap_png_bound(ctx) : s360_frame_png_bound(ctx);
+  if (m == OutMode::JpegDevice) return cubemap ? s360_frame_cubemap_jpeg_bound(ctx) : s360_frame_jpeg_bound(ctx);
+  return (size_t)w * h * 3;
+}
+// a finished output of slot `slot` (-1: the selected one) into buf: the file (*n its size) or the pixels
+void fetch_output(s360_ctx* ctx, OutMode m, bool cubemap, int slot, int age, uint8_t* buf, size_t cap, size_t* n) {
+  int rc;
+  if (m == OutMode::PngDevice) {
+    rc = cubemap ? (slot < 0 ? s360_frame_download_cubemap_png(ctx, age, buf, cap, n) : s360_frame_download_cubemap_png_slot(ctx, slot, age, buf, cap, n))
+                 : (slot < 0 ? s360_frame_download_png(ctx, age, buf, cap, n) : s360_frame_download_png_slot(ctx, slot, age, buf, cap, n));
+  } else if (m == OutMode::JpegDevice) {
+    rc = cubemap ? (slot < 0 ? s360_frame_download_cubemap_jpeg(ctx, age, buf, cap, n) : s360_frame_download_cubemap_jpeg_slot(ctx, slot, age, buf, cap, n))
+                 : (slot < 0 ? s360_frame_download_jpeg(ctx, age, buf, cap, n) : s360_frame_download_jpeg_slot(ctx, slot, age, buf, cap, n));
+  } else {
+    rc = cubemap ? (slot < 0 ? s360_frame_download_cubemap(ctx, age, buf) : s360_frame_download_cubemap_slot(ctx, slot, age, buf))
+                 : (slot < 0 ? s360_frame_download_equirect_of(ctx, age, buf) : s360_frame_download_equirect_slot(ctx, slot, age, buf));
+  }
+  ck(rc, ctx);
+}
+void save_jpeg(const std::string& path, const uint8_t* px, int w, int h) {
+  std::vector<uint8_t> file;
+  try {
+    file = jpegio::encode(px, w, h, 95);  // cv::imwrite's default quality
+  } catch (const std::exception& e) {
+    die(e.what());
+  }
+  save_bytes(path, file.data(), file.size());
+}
+// ... and onto the disk, on a writer thread: n bytes of a file, or w x h pixels through the path's host encoder
+void write_output(OutMode m, const std::string& path, const uint8_t* data, size_t n, int w, int h) {
+  if (is_file(m)) save_bytes(path, data, n);
+  else if (m == OutMode::JpegHost) save_jpeg(path, data, w, h);
+  else save_png(path, data, w, h, 3);
 }
 
 // One decoded frame of the rig (rig.loadSideCameraImages: one thread per camera, RigDescription.cpp:80-108)
@@ -1105,15 +1190,16 @@ static int run_job(const Flags& flags) {
     ck(s360_set_frame_pipelining(J.ctx[0], 1), J.ctx[0]);  // pole stage of frame k overlaps side stage of k+1
   }
   if (!F.s("bin_list").empty()) open_bins(J);
-  const bool devPng = F.b("device_png");
-  if (devPng) ck(s360_set_png_encode(J.ctx[0], 1), J.ctx[0]);  // (the root composites and holds the output)
-
   const s360_geometry& g = J.g;
   const std::string prev = F.s("prev_frame_data_dir");
   const bool cube = F.i("cubemap_width") > 0 && F.i("cubemap_height") > 0 && !F.s("output_cubemap_path").empty();
+  const OutMode eqMode = out_mode(F, F.s("output_equirect_path")), cmMode = out_mode(F, F.s("output_cubemap_path"));
   // a stream leaves the cubemap of EVERY frame (the reference's caller asks for one beside every equirect,
-  // batch_process_video.py:40-47): rendered with the frame, fetched and written beside its equirect
-  const bool cubeStream = cube && numFrames > 1;
+  // batch_process_video.py:40-47): rendered with the frame, fetched and written beside its equirect; so does a single frame whose
+  // cubemap the device encodes as a JPEG (the encoder sits behind the frame's last kernel)
+  const bool cubeStream = cube && (numFrames > 1 || cmMode == OutMode::JpegDevice);
+  enable_output_encoders(J.ctx[0], eqMode, cubeStream, cmMode);  // (the root composites and holds the output)
+  if (verbose >= 1) report_output_paths(eqMode, cube, cubeStream || cmMode == OutMode::JpegHost ? cmMode : OutMode::PngHost);
   int cubeWhc[3] = {0, 0, 0};
   if (cubeStream) {
     ck(s360_set_cubemap_output(J.ctx[0], F.i("cubemap_width"), F.i("cubemap_height"), F.s("cubemap_format").c_str()), J.ctx[0]);
@@ -1132,7 +1218,7 @@ static int run_job(const Flags& flags) {
 
   // Up to two finished frames are PNG-encoded and written while the next one renders (one encoder per frame, parallel
   // deflate inside it): an 8192 x 8192 file takes longer to encode and write than the frame takes to render.
-  const size_t outBytes = devPng ? s360_frame_png_bound(J.ctx[0]) : (size_t)g.out_width * g.out_height * 3;
+  const size_t outBytes = output_buffer_bytes(J.ctx[0], eqMode, false, g.out_width, g.out_height);
   constexpr int kMaxEncoders = 4;
   const char* encEnv = std::getenv("S360_ENCODERS");  // (developer switch)
   const int kEncoders = std::max(1, std::min(kMaxEncoders, encEnv ? std::atoi(encEnv) : 3));
@@ -1141,7 +1227,7 @@ static int run_job(const Flags& flags) {
   pngio::Pixels outBuf[kMaxEncoders + 1];
   std::thread encoder[kMaxEncoders + 1];  // encoder[i] owns outBuf[i] while it runs
   for (int i = 0; i <= kEncoders; ++i) outBuf[i].resize(numFrames > 1 || i == 0 ? outBytes : 0);
-  const size_t cubeBytes = !cubeStream ? 0 : devPng ? s360_frame_cubemap_png_bound(J.ctx[0]) : (size_t)cubeWhc[0] * cubeWhc[1] * 3;
+  const size_t cubeBytes = !cubeStream ? 0 : output_buffer_bytes(J.ctx[0], cmMode, true, cubeWhc[0], cubeWhc[1]);
   pngio::Pixels cubeBuf[kMaxEncoders + 1];  // the frame's cubemap travels with its equirect: same fetch, same writer thread
   for (int i = 0; i <= kEncoders && cubeStream; ++i) cubeBuf[i].resize(cubeBytes);
   int cur = 0;  // the buffer the next download goes to
@@ -1201,14 +1287,10 @@ static int run_job(const Flags& flags) {
     }
     const double tf = now_sec();
     size_t pngBytes = 0;
-    if (devPng) ck(s360_frame_download_png(J.ctx[0], last ? 0 : 1, outBuf[cur].data(), outBuf[cur].size(), &pngBytes), J.ctx[0]);
-    else if (last) ck(s360_frame_download_equirect(J.ctx[0], outBuf[cur].data()), J.ctx[0]);
-    else ck(s360_frame_download_equirect_of(J.ctx[0], 1, outBuf[cur].data()), J.ctx[0]);  // frame k, while k+1 renders
+    if (!is_file(eqMode) && last) ck(s360_frame_download_equirect(J.ctx[0], outBuf[cur].data()), J.ctx[0]);
+    else fetch_output(J.ctx[0], eqMode, false, -1, last ? 0 : 1, outBuf[cur].data(), outBuf[cur].size(), &pngBytes);  // frame k, while k+1 renders
     size_t cubePngBytes = 0;
-    if (cubeStream) {
-      if (devPng) ck(s360_frame_download_cubemap_png(J.ctx[0], last ? 0 : 1, cubeBuf[cur].data(), cubeBuf[cur].size(), &cubePngBytes), J.ctx[0]);
-      else ck(s360_frame_download_cubemap(J.ctx[0], last ? 0 : 1, cubeBuf[cur].data()), J.ctx[0]);
-    }
+    if (cubeStream) fetch_output(J.ctx[0], cmMode, true, -1, last ? 0 : 1, cubeBuf[cur].data(), cubeBuf[cur].size(), &cubePngBytes);
     if (!leaving.empty()) {  // frame k is complete, so frame k+1's uploads (enqueued before it rendered) are long done
       ck(s360_frame_uploads_complete(J.ctx[0]), J.ctx[0]);
       for (auto& fi : leaving) spare.push_back(std::move(fi));
@@ -1223,16 +1305,10 @@ static int run_job(const Flags& flags) {
     const std::string cubePath = cubeStream ? frame_path(F.s("output_cubemap_path"), frame) : std::string();
     const uint8_t* cpx = cubeStream ? cubeBuf[cur].data() : nullptr;
     const int cw = cubeWhc[0], chh = cubeWhc[1];
-    if (devPng)
-      encoder[cur] = std::thread([px, outPath, pngBytes, cpx, cubePath, cubePngBytes] {
-        save_bytes(outPath, px, pngBytes);
-        if (cpx) save_bytes(cubePath, cpx, cubePngBytes);
-      });
-    else
-      encoder[cur] = std::thread([px, outPath, &g, cpx, cubePath, cw, chh] {
-        save_png(outPath, px, g.out_width, g.out_height, 3);  // TRSP:961
-        if (cpx) save_png(cubePath, cpx, cw, chh, 3);          // TRSP:935
-      });
+    encoder[cur] = std::thread([=, &g] {
+      write_output(eqMode, outPath, px, pngBytes, g.out_width, g.out_height);   // TRSP:961
+      if (cpx) write_output(cmMode, cubePath, cpx, cubePngBytes, cw, chh);  // TRSP:935
+    });
     // the reference writes the state of every frame; a stream only needs it to resume after its last frame. (Beside the
     // equirect's encoder, not in front of it.)
     if (F.b("write_state") && last) write_state(J, frame);
@@ -1242,7 +1318,8 @@ static int run_job(const Flags& flags) {
       ck(s360_frame_cubemap(J.ctx[0], F.i("cubemap_width"), F.i("cubemap_height"), F.s("cubemap_format").c_str(), whc, nullptr), J.ctx[0]);
       std::vector<uint8_t> cubeImg((size_t)whc[0] * whc[1] * 3);
       ck(s360_frame_cubemap(J.ctx[0], F.i("cubemap_width"), F.i("cubemap_height"), F.s("cubemap_format").c_str(), whc, cubeImg.data()), J.ctx[0]);
-      save_png(frame_path(F.s("output_cubemap_path"), frame), cubeImg.data(), whc[0], whc[1], 3);  // (a stream segment of one frame is named like the others)
+      // (a stream segment of one frame is named like the others; pixels in hand: the path's host encoder)
+      write_output(cmMode == OutMode::JpegHost ? cmMode : OutMode::PngHost, frame_path(F.s("output_cubemap_path"), frame), cubeImg.data(), 0, whc[0], whc[1]);
     }
     cur = numFrames > 1 ? (cur + 1) % (kEncoders + 1) : 0;
     const double tj = now_sec();
@@ -1323,9 +1400,10 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
   }
   ck(s360_set_sweep_mode(ctx, "throughput"), ctx);  // many flows per launch: the kernel with the fewest instructions per pixel
   const s360_geometry& g = J.g;
-  const bool devPng = F.b("device_png");
-  if (devPng) ck(s360_set_png_encode(ctx, 1), ctx);
-  const size_t outBytes = devPng ? s360_frame_png_bound(ctx) : (size_t)g.out_width * g.out_height * 3;
+  const OutMode eqMode = out_mode(F, F.s("output_equirect_path")), cmMode = out_mode(F, F.s("output_cubemap_path"));
+  enable_output_encoders(ctx, eqMode, cube, cmMode);
+  if (verbose >= 1) report_output_paths(eqMode, cube, cmMode);
+  const size_t outBytes = output_buffer_bytes(ctx, eqMode, false, g.out_width, g.out_height);
   std::vector<size_t> pngBytes(S, 0);
   // the cubemap of every frame of every stream (batch_process_video.py:40-47), rendered for all slots of a step in one launch
   int cubeWhc[3] = {0, 0, 0};
@@ -1333,7 +1411,7 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
     ck(s360_set_cubemap_output(ctx, F.i("cubemap_width"), F.i("cubemap_height"), F.s("cubemap_format").c_str()), ctx);
     ck(s360_frame_cubemap_size(ctx, cubeWhc), ctx);
   }
-  const size_t cubeBytes = !cube ? 0 : devPng ? s360_frame_cubemap_png_bound(ctx) : (size_t)cubeWhc[0] * cubeWhc[1] * 3;
+  const size_t cubeBytes = !cube ? 0 : output_buffer_bytes(ctx, cmMode, true, cubeWhc[0], cubeWhc[1]);
   std::vector<size_t> cubePngBytes(S, 0);
   std::vector<pngio::Pixels> cubeBuf(cube ? S : 0);
   for (auto& b : cubeBuf) b.resize(cubeBytes);
@@ -1408,12 +1486,8 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
         if (k < segs[s].n) {
           const int age = (more && k + 1 < segs[s].n) ? 1 : 0;  // the slot's latest enqueued frame is k+1 unless its stream has ended
           // (the first fetch of a step waits for the step)
-          if (devPng) ck(s360_frame_download_png_slot(ctx, s, age, outBuf[s].data(), outBuf[s].size(), &pngBytes[s]), ctx);
-          else ck(s360_frame_download_equirect_slot(ctx, s, age, outBuf[s].data()), ctx);
-          if (cube) {
-            if (devPng) ck(s360_frame_download_cubemap_png_slot(ctx, s, age, cubeBuf[s].data(), cubeBuf[s].size(), &cubePngBytes[s]), ctx);
-            else ck(s360_frame_download_cubemap_slot(ctx, s, age, cubeBuf[s].data()), ctx);
-          }
+          fetch_output(ctx, eqMode, false, s, age, outBuf[s].data(), outBuf[s].size(), &pngBytes[s]);
+          if (cube) fetch_output(ctx, cmMode, true, s, age, cubeBuf[s].data(), cubeBuf[s].size(), &cubePngBytes[s]);
           if (F.b("write_state") && k + 1 == segs[s].n) {
             std::lock_guard<std::mutex> sel(selMu);
             ck(s360_select_frame_slot(ctx, s), ctx);
@@ -1436,16 +1510,10 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
           const uint8_t* cpx = cube ? cubeBuf[s].data() : nullptr;
           const size_t cnb = cubePngBytes[s];
           const int cw = cubeWhc[0], chh = cubeWhc[1];
-          if (devPng)
-            encoder[s] = std::thread([px, outPath, nb, cpx, cubePath, cnb] {
-              save_bytes(outPath, px, nb);
-              if (cpx) save_bytes(cubePath, cpx, cnb);
-            });
-          else
-            encoder[s] = std::thread([px, outPath, &g, cpx, cubePath, cw, chh] {
-              save_png(outPath, px, g.out_width, g.out_height, 3);
-              if (cpx) save_png(cubePath, cpx, cw, chh, 3);
-            });
+          encoder[s] = std::thread([=, &g] {
+            write_output(eqMode, outPath, px, nb, g.out_width, g.out_height);
+            if (cpx) write_output(cmMode, cubePath, cpx, cnb, cw, chh);
+          });
           name[s] = next_frame_name(name[s]);
         }
     }

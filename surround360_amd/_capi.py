@@ -111,6 +111,11 @@ INPUT_JPEG_SYMBOLS = ("s360_input_jpeg_decodable", "s360_decode_input_jpeg_batch
                       "s360_jpeg_decode_failure")
 # ... and its test tap, include/s360_debug_input_jpeg.h
 DEBUG_INPUT_JPEG_SYMBOLS = ("s360_debug_input_jpeg_blocks",)
+# ... and every symbol include/s360_frame_jpeg.h declares (a finished frame's equirect and cubemap as JPEG files encoded on the device)
+FRAME_JPEG_SYMBOLS = ("s360_set_jpeg_encode", "s360_frame_jpeg_bound", "s360_frame_cubemap_jpeg_bound", "s360_frame_download_jpeg",
+                      "s360_frame_download_jpeg_slot", "s360_frame_download_cubemap_jpeg", "s360_frame_download_cubemap_jpeg_slot")
+# ... and its test tap, include/s360_debug_frame_jpeg.h
+DEBUG_FRAME_JPEG_SYMBOLS = ("s360_debug_frame_jpeg",)
 # ... and the test taps include/s360_debug.h declares (not part of the API)
 DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
 # ... and the one include/s360_debug_final_flow.h declares
@@ -242,6 +247,20 @@ def lib():
         L.s360_jpeg_decode_failure.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.s360_debug_input_jpeg_blocks.restype = C.c_int
         L.s360_debug_input_jpeg_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.s360_set_jpeg_encode.restype = C.c_int
+        L.s360_set_jpeg_encode.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        for name in ("s360_frame_jpeg_bound", "s360_frame_cubemap_jpeg_bound"):
+            getattr(L, name).restype = C.c_size_t
+            getattr(L, name).argtypes = [C.c_void_p]
+        for name in ("s360_frame_download_jpeg", "s360_frame_download_cubemap_jpeg"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        for name in ("s360_frame_download_jpeg_slot", "s360_frame_download_cubemap_jpeg_slot"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.s360_debug_frame_jpeg.restype = C.c_int
+        L.s360_debug_frame_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t] + \
+                                           [C.POINTER(C.c_size_t)] * 3 + [C.POINTER(C.c_float)]
         L.s360_debug_isp_stages.restype = C.c_int
         L.s360_debug_isp_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8
         L.s360_debug_flow_level.restype = C.c_int

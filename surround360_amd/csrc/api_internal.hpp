@@ -23,6 +23,14 @@ void prev_pole_arrived(s360_ctx* c, FrameState& F, int unit, unsigned bits);
 void prev_pr_arrived(FrameState& F, unsigned bits);
 // api_png.hip: host threads for a PNG file's CRCs (developer switch S360_PNG_CRC_THREADS)
 int png_crc_threads();
+// api_png.hip: what the fetches of a finished frame share. A refused slot number; the state of frame slot `slot` (-1: the selected
+// one); the download stream with its event and the error words' landing area; the output buffer that holds the frame `age` frames
+// back, and that frame's cubemap
+constexpr int kNoSlot = -2;
+FrameState& slot_state(s360_ctx* c, int slot);
+void ensure_download_stream(s360_ctx* c);
+int frame_buffer(s360_ctx* c, FrameState& F, int age);
+int cube_buffer(s360_ctx* c, FrameState& F, int age);
 
 inline void h2d(s360_ctx* c, void* d, const void* h, size_t n) {
   S360_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, c->st));

@@ -17,14 +17,10 @@ int png_crc_threads() {
   const int n = e ? std::atoi(e) : 4;
   return n < 1 ? 1 : (n > 64 ? 64 : n);
 }
-}  // namespace s360
-
-extern "C" {
-
-constexpr int kNoSlot = -2;  // a refused slot number
+// ---- what the fetches of a finished frame share (api_internal.hpp; api_frame_jpeg.hip uses them too) ----
 // the state of frame slot `slot` (-1: the selected one) without touching the selection: a fetching thread names its slot, so that
 // the thread that feeds the context can go on selecting slots for its uploads
-static FrameState& slot_state(s360_ctx* c, int slot) {
+FrameState& slot_state(s360_ctx* c, int slot) {
   if (slot < 0) return frame_state(c);
   need(slot < (int)std::max<size_t>(c->slots.size(), 1), "frame slot out of range");
   const int saved = c->slot;
@@ -32,8 +28,8 @@ static FrameState& slot_state(s360_ctx* c, int slot) {
   struct Restore { s360_ctx* c; int s; ~Restore() { c->slot = s; } } restore{c, saved};
   return frame_state(c);
 }
-// what the fetches of a finished frame share: the download stream, the event its host thread sleeps on, the error words' landing area
-static void ensure_download_stream(s360_ctx* c) {
+// the download stream, the event its host thread sleeps on, the error words' landing area
+void ensure_download_stream(s360_ctx* c) {
   if (!c->stDown) S360_HIP(hipStreamCreateWithFlags(&c->stDown, hipStreamNonBlocking));
   if (!c->evDown) S360_HIP(hipEventCreateWithFlags(&c->evDown, hipEventDisableTiming | hipEventBlockingSync));
   if (!c->downErr.p) {
@@ -42,12 +38,23 @@ static void ensure_download_stream(s360_ctx* c) {
   }
 }
 // the output buffer that holds the frame `age` frames back (0 = latest enqueued frame, 1 = the one before)
-static int frame_buffer(s360_ctx* c, FrameState& F, int age) {
+int frame_buffer(s360_ctx* c, FrameState& F, int age) {
   need(F.frames_done > age, "that frame has not been rendered");
   need(age == 0 || ((c->pipeline || c->two_outputs) && F.outBGR[F.out_cur ^ 1].p),
        "age 1 needs two output buffers (s360_set_frame_pipelining or s360_set_output_double_buffer)");
   return age == 0 ? F.out_cur : F.out_cur ^ 1;
 }
+// ... and that frame's cubemap (s360_set_cubemap_output)
+int cube_buffer(s360_ctx* c, FrameState& F, int age) {
+  const int b = frame_buffer(c, F, age);
+  if (F.cubeFrame[b] != F.frames_done - 1 - age || !F.cubeBGR[b].p)
+    throw Error(S360_ERR_STATE, "that frame was rendered without s360_set_cubemap_output");
+  return b;
+}
+}  // namespace s360
+
+extern "C" {
+
 // `bytes` bytes at `src`, which belong to output buffer b of slot F (the stacked equirect, the cubemap), into the caller's buffer
 static void fetch_frame_bytes(s360_ctx* c, std::unique_lock<std::recursive_mutex>& lk, FrameState& F, int b, const void* src, size_t bytes,
                               uint8_t* out) {
@@ -73,13 +80,6 @@ static void fetch_frame_bytes(s360_ctx* c, std::unique_lock<std::recursive_mutex
   // the frame's sweep error words were snapshotted in front of outDone[b] (render.hpp): a timed-out banded sweep
   // fails THIS frame's download, before the host hands the pixels to an encoder
   if (errw) check_sweep_error(c, errw);
-}
-// ... and that frame's cubemap (s360_set_cubemap_output)
-static int cube_buffer(s360_ctx* c, FrameState& F, int age) {
-  const int b = frame_buffer(c, F, age);
-  if (F.cubeFrame[b] != F.frames_done - 1 - age || !F.cubeBGR[b].p)
-    throw Error(S360_ERR_STATE, "that frame was rendered without s360_set_cubemap_output");
-  return b;
 }
 // the stacked equirect, or (`cube`) the stacked cubemap, of the frame `age` frames back of a slot (-1: the selected one; the
 // _slot entry points, which name their slot, pass a negative one on as kNoSlot)

@@ -8,6 +8,7 @@
 #include "core.hpp"
 #include "flow.hpp"
 #include "png.hpp"
+#include "jpeg.hpp"
 #include "jpeg_decode.hpp"
 #include "png_decode.hpp"
 #include "rig.hpp"
@@ -46,6 +47,13 @@ struct s360_ctx {
   s360::PinBuf downErr;          // ... and that frame's sweep error words (copied on stDown with the pixels)
   bool png_encode = false;       // s360_set_png_encode: every finished frame is also encoded as a PNG on the device
   s360::PinBuf pngMetaHost;      // landing area of a frame's band table (s360_frame_download_png)
+  // s360_set_jpeg_encode: every finished frame is also encoded as a baseline JPEG on the device (jpeg.hip). ONE encoder per context,
+  // created by the first frame that needs it (render.hip frame_jpeg_encoder) and sized for the larger of the equirect and the
+  // cubemap: the encodes of a step are serial on the finish stream anyway. Nothing of it exists while the switch has never been on.
+  bool jpeg_encode = false;
+  int jpeg_quality = 95;
+  s360::JpegEncoder frameJpeg;
+  s360::PinBuf jpegDown;  // landing area of a frame's scan size when the fetch could not know it up front (s360_frame_download_jpeg)
   // A batch of PNG files encoded by one launch sequence (png_batch_enqueue): the state images of a frame
   // (s360_frame_encode_state_pngs -> statePng) and the operator form (s360_encode_png_batch -> opPng). Buffers are allocated on
   // first use, grow only, and belong to the context. `gen` counts the encode calls: a fetch that finds another batch after its

@@ -16,8 +16,19 @@
 //   k_jpeg_stuff_count /   the last partial byte filled with 1-bits, then 0x00 after every 0xFF: count per tile of 4096 bytes,
 //   k_scan_* / _scatter    the same scan, scatter
 //
-// Everything is enqueued on the caller's stream, the memset of the word buffer included; nothing synchronises. Buffers are sized
-// for the worst case (1660 bits a block, doubled by stuffing) and every store is bounds-checked besides.
+// Everything is enqueued on the caller's stream, the memset of the word buffer included; nothing synchronises. The encoder's own
+// buffers are sized for the worst case (1660 bits a block, doubled by stuffing) and every store is bounds-checked besides. The
+// caller's scan buffer may be smaller (encode(.., capped): a frame slot's, render.hip): the stuffed size is known from the tile
+// scan before k_jpeg_stuff_scatter runs, which then stores the whole scan or, when it does not fit, nothing; count[0] tells.
+//
+// Sizes: 8192 x 8192 (a frame slot's stereo equirect) is 262 144 MCUs, 1 572 864 blocks: 65 536 workgroups of k_jpeg_blocks,
+// 393 216 of k_jpeg_entropy (x 256 threads: below 2^32 work-items), 1536 scan groups, at most 79 680 stream tiles; bit offsets
+// reach 2.6e9 in the worst case and are unsigned 32-bit in every kernel (blk, off[], nbits, base and i of the stuffing kernels;
+// byte offsets into out[] are size_t). JPEG_MAX_MCUS keeps all of them below 2^32.
+//
+// gfx950, VGPRs / SGPRs / LDS bytes (no scratch, no spills): k_jpeg_blocks 50/97/6240, k_jpeg_entropy<false> 11/28/0, <true>
+// 15/30/896, k_scan_totals 8/14/1024, k_scan_groups 18/32/1024, k_scan_apply 10/22/1024, k_jpeg_stuff_count 5/19/1024,
+// k_jpeg_stuff_scatter 24/24/1024.
 #include "jpeg.hpp"
 
 #include <cstring>
@@ -378,7 +389,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_jpeg_stuff_scatter(const unsigne
                                                                    unsigned* __restrict__ count) {
   __shared__ unsigned sh[ST_THREADS];
   const unsigned nbits = *nbitsp, nbytes = (nbits + 7) >> 3;
-  if (blockIdx.x == 0 && threadIdx.x == 0) count[0] = nbytes + *nff;
+  const unsigned stuffed = nbytes + *nff;  // (at most twice 326 MB: 32 bits hold it)
+  if (blockIdx.x == 0 && threadIdx.x == 0) count[0] = stuffed;
+  if (stuffed > cap) return;  // a scan that does not fit is not stored at all; count[0] > cap tells (uniform over the grid)
   const unsigned base = blockIdx.x * JPEG_STUFF_TILE + threadIdx.x * ST_PER;
   if (blockIdx.x * (unsigned)JPEG_STUFF_TILE >= nbytes) return;  // (uniform over the workgroup)
   unsigned x[ST_PER], c = 0;
@@ -412,8 +425,14 @@ void scan(const unsigned* in, unsigned n, unsigned* gtot, unsigned* goff, unsign
 
 void JpegEncoder::init(int max_w, int max_h, int quality_, hipStream_t st) {
   if (!jpeg_size_ok(max_w, max_h)) throw Error(S360_ERR_INVALID_ARG, "jpeg: image size outside 1..65535 or more than 431 220 MCUs of 16 x 16 pixels");
+  init_mcus(jpeg_mcus(max_w, max_h), quality_, st);
   maxW = max_w;
   maxH = max_h;
+}
+void JpegEncoder::init_mcus(long long max_mcus, int quality_, hipStream_t st) {
+  if (max_mcus < 1 || max_mcus > JPEG_MAX_MCUS) throw Error(S360_ERR_INVALID_ARG, "jpeg: more than 431 220 MCUs of 16 x 16 pixels");
+  maxW = maxH = 65535;
+  maxMcus = max_mcus;
   quality = quality_ < 1 ? 1 : quality_ > 100 ? 100 : quality_;  // as jpegio::encode clamps
   const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2;  // jpeg_quality_scaling
   JpegTab tab;
@@ -428,7 +447,7 @@ void JpegEncoder::init(int max_w, int max_h, int quality_, hipStream_t st) {
   huff_table(kAcLumBits, kAcLumVals, tab.ac[0], 256);
   huff_table(kAcChrBits, kAcChrVals, tab.ac[1], 256);
   for (int i = 0; i < 64; ++i) tab.zz[i] = kZigzag[i];
-  const size_t nblk = (size_t)jpeg_mcus(max_w, max_h) * 6, raw = jpeg_raw_cap(max_w, max_h);
+  const size_t nblk = (size_t)max_mcus * 6, raw = jpeg_raw_cap_mcus(max_mcus);
   const size_t ntiles = cdiv(raw, JPEG_STUFF_TILE), nscan = nblk > ntiles ? nblk : ntiles;
   dTab.ensure(sizeof tab);
   dCoef.ensure(nblk * 64 * sizeof(int16_t));
@@ -444,10 +463,10 @@ void JpegEncoder::init(int max_w, int max_h, int quality_, hipStream_t st) {
   S360_HIP(hipStreamSynchronize(st));  // (tab goes out of scope)
 }
 
-void JpegEncoder::encode(const uint8_t* bgr, int w, int h, uint8_t* scan_out, size_t scan_cap, uint32_t* count, hipStream_t st) {
-  if (w < 1 || h < 1 || w > maxW || h > maxH || jpeg_mcus(w, h) > jpeg_mcus(maxW, maxH))
+void JpegEncoder::encode(const uint8_t* bgr, int w, int h, uint8_t* scan_out, size_t scan_cap, uint32_t* count, hipStream_t st, bool capped) {
+  if (w < 1 || h < 1 || w > maxW || h > maxH || jpeg_mcus(w, h) > maxMcus)
     throw Error(S360_ERR_INVALID_ARG, "jpeg: the image is larger than the encoder was created for");
-  if (scan_cap < jpeg_scan_cap(w, h)) throw Error(S360_ERR_INVALID_ARG, "jpeg: the scan buffer is smaller than jpeg_scan_cap");
+  if (!capped && scan_cap < jpeg_scan_cap(w, h)) throw Error(S360_ERR_INVALID_ARG, "jpeg: the scan buffer is smaller than jpeg_scan_cap");
   const int mcux = (w + 15) / 16, nmcu = (int)jpeg_mcus(w, h);
   const unsigned nblk = (unsigned)nmcu * 6;
   const size_t raw = jpeg_raw_cap(w, h);

@@ -19,20 +19,31 @@ constexpr long long JPEG_MAX_MCUS = 0xFFFFFFFFll / (6 * JPEG_MAX_BLOCK_BITS) - 1
 
 inline long long jpeg_mcus(int w, int h) { return (long long)((w + 15) / 16) * ((h + 15) / 16); }
 // bytes of the scan before stuffing, rounded up to whole words; stuffing at most doubles it
-inline size_t jpeg_raw_cap(int w, int h) { return (((size_t)jpeg_mcus(w, h) * 6 * JPEG_MAX_BLOCK_BITS + 7) / 8 + 3) / 4 * 4; }
+inline size_t jpeg_raw_cap_mcus(long long mcus) { return (((size_t)mcus * 6 * JPEG_MAX_BLOCK_BITS + 7) / 8 + 3) / 4 * 4; }
+inline size_t jpeg_raw_cap(int w, int h) { return jpeg_raw_cap_mcus(jpeg_mcus(w, h)); }
 inline size_t jpeg_scan_cap(int w, int h) { return 2 * jpeg_raw_cap(w, h); }
 inline size_t jpeg_file_bound(int w, int h) { return JPEG_HEADER_BYTES + jpeg_scan_cap(w, h) + 2; }
+// The scan buffers a frame slot keeps (s360_set_jpeg_encode, include/s360_frame_jpeg.h) are not the worst case: 768 bytes per MCU,
+// the size of the MCU's own 16 x 16 B,G,R pixels (the worst case is 2490). A scan that needs more is refused, never cut short.
+constexpr size_t JPEG_FRAME_MCU_BYTES = 16 * 16 * 3;
+inline size_t jpeg_frame_scan_cap(int w, int h) { return (size_t)jpeg_mcus(w, h) * JPEG_FRAME_MCU_BYTES; }
 inline bool jpeg_size_ok(int w, int h) { return w >= 1 && h >= 1 && w <= 65535 && h <= 65535 && jpeg_mcus(w, h) <= JPEG_MAX_MCUS; }
 
 struct JpegEncoder {
   int maxW = 0, maxH = 0, quality = 95;
+  long long maxMcus = 0;  // what the buffers hold: jpeg_mcus(maxW, maxH), or what init_mcus was given
   int q[2][64];  // quantisation tables, natural order
   DevBuf dTab, dCoef, dBlkBits, dBlkOff, dGrpTot, dGrpOff, dWords, dTileCnt, dTileOff, dTotals;
   // allocates for images up to max_w x max_h and uploads the tables on `st` (which is synchronised before returning)
   void init(int max_w, int max_h, int quality_, hipStream_t st);
+  // ... for images of any shape with up to max_mcus MCUs of 16 x 16 pixels (1..JPEG_MAX_MCUS): an encoder that serves images of
+  // several shapes (a frame's equirect and its cubemap) is sized by the largest of them, not by the box around them
+  void init_mcus(long long max_mcus, int quality_, hipStream_t st);
   // Enqueues the whole encoder on `st`; nothing synchronises. bgr: device memory, h rows of w x 3 bytes. scan: device memory of
-  // scan_cap >= jpeg_scan_cap(w, h) bytes, receives the entropy-coded segment (stuffed, padded); count[0] its byte count.
-  void encode(const uint8_t* bgr, int w, int h, uint8_t* scan, size_t scan_cap, uint32_t* count, hipStream_t st);
+  // scan_cap bytes, receives the entropy-coded segment (stuffed, padded); count[0] its byte count. scan_cap >= jpeg_scan_cap(w, h)
+  // holds every scan, and a smaller one is refused here unless `capped`: then a scan of more than scan_cap bytes is not stored at
+  // all — not one byte of it — and count[0] > scan_cap is how the caller learns of it, and of the size it needed.
+  void encode(const uint8_t* bgr, int w, int h, uint8_t* scan, size_t scan_cap, uint32_t* count, hipStream_t st, bool capped = false);
   // the JPEG_HEADER_BYTES bytes in front of the scan
   void header(uint8_t* out, int w, int h) const;
   // test tap: after encode() has run, the coefficient blocks and their bit lengths (device pointers)

@@ -807,6 +807,34 @@ struct FinishStream {
 };
 }  // namespace
 
+JpegEncoder& frame_jpeg_encoder(s360_ctx* c, long long mcus, hipStream_t st) {
+  JpegEncoder& E = c->frameJpeg;
+  const int q = c->jpeg_quality;
+  if (mcus > E.maxMcus || q != E.quality) {
+    // (growing frees the old buffers, which waits for the device; the tables' upload is ordered behind the encodes already on `st`)
+    E.init_mcus(std::max(mcus, E.maxMcus), q, st);
+  }
+  return E;
+}
+namespace {
+// s360_set_jpeg_encode: the image `bgr` of output buffer ob of slot F as a JPEG scan behind the kernels that wrote it (k = 0 the
+// equirect, 1 the cubemap); the scan's size lands in the slot's page-locked words in front of outDone[ob]
+void frame_jpeg_enqueue(s360_ctx* c, FrameState& F, int ob, int k, const uint8_t* bgr, int w, int h, long long mcus, hipStream_t st) {
+  if (!jpeg_size_ok(w, h)) throw Error(S360_ERR_INVALID_ARG, "s360_set_jpeg_encode: a JPEG file holds at most 65535 x 65535 pixels and this encoder 431 220 MCUs of 16 x 16");
+  JpegEncoder& E = frame_jpeg_encoder(c, mcus, st);
+  FrameState::JpegOut& J = F.jpeg[k];
+  J.cap[ob] = jpeg_frame_scan_cap(w, h);
+  J.scan[ob].ensure(J.cap[ob]);
+  F.jpegCount[ob].ensure(2 * sizeof(uint32_t));
+  F.jpegCountPin[ob].ensure(2 * sizeof(uint32_t));
+  J.hdr[ob].resize(JPEG_HEADER_BYTES);
+  E.header(J.hdr[ob].data(), w, h);
+  E.encode(bgr, w, h, J.scan[ob].as<uint8_t>(), J.cap[ob], F.jpegCount[ob].as<uint32_t>() + k, st, true);
+  S360_HIP(hipMemcpyAsync(F.jpegCountPin[ob].as<uint32_t>() + k, F.jpegCount[ob].as<uint32_t>() + k, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  J.frame[ob] = F.frames_done;
+}
+}  // namespace
+
 // Pole stage + composite of a set of frame slots: per slot panorama assembly, pole projections and the flow inputs of
 // the enabled pole units; then the pole flows of ALL slots in one FlowEngine batch (two when the top and bottom pole
 // projections differ in height); then per slot warp, composite, sharpen / final resize / stacking.
@@ -1126,6 +1154,12 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
         png_encode_enqueue(st, F.cubeBGR[ob].as<uint8_t>(), F.cubePngPlan[ob], F.sc->pngScratch, F.cubePngMeta[ob],
                            F.cubePngFile[ob].as<uint8_t>());
         F.cubePngFrame[ob] = F.frames_done;
+      }
+      if (c->jpeg_encode) {  // ... and cv::imwrite's JpegEncoder for a .jpg path, on the device: jpeg.hip (include/s360_frame_jpeg.h)
+        ProfScope ps(prof, "jpeg_encode");
+        const long long mcus = std::max(jpeg_mcus(outW, outH), cube ? jpeg_mcus(F.cubeOutW[ob], F.cubeOutH[ob]) : 0ll);
+        frame_jpeg_enqueue(c, F, ob, 0, F.outBGR[ob].as<uint8_t>(), outW, outH, mcus, st);
+        if (cube) frame_jpeg_enqueue(c, F, ob, 1, F.cubeBGR[ob].as<uint8_t>(), F.cubeOutW[ob], F.cubeOutH[ob], mcus, st);
       }
       if (!F.outErrDev[ob].p) {
         F.outErrDev[ob].ensure(4 * sizeof(unsigned));

@@ -123,6 +123,20 @@ struct FrameState {
   DevBuf cubePngFile[2], cubePngMeta[2];
   PngPlan cubePngPlan[2];
   long long cubePngFrame[2] = {-1, -1};
+  // s360_set_jpeg_encode: the frame in outBGR[i] / cubeBGR[i] also as the scan of a baseline JPEG file (jpeg.hip), written by the
+  // finish stage in front of outDone[i]. k = 0 the equirect, 1 the cubemap. scan: jpeg_frame_scan_cap bytes, NOT the format's worst
+  // case; count[i]: two device words, each scan's size in bytes — larger than cap when the scan did not fit and was not stored;
+  // countPin[i]: their copy in page-locked memory, valid once outDone[i] has fired (a fetch then knows the size before it
+  // enqueues its copy); hdr: the 623 bytes in front of the scan, kept with the frame so that a change of quality or size never
+  // mixes tables; frame: the frame (frames_done) all that belongs to. Allocated only while the feature is on.
+  struct JpegOut {
+    DevBuf scan[2];
+    size_t cap[2] = {0, 0};
+    std::vector<uint8_t> hdr[2];
+    long long frame[2] = {-1, -1};
+  } jpeg[2];
+  DevBuf jpegCount[2];
+  PinBuf jpegCountPin[2];
 };
 
 // kExtendFrac (TRSP:400-401, 507): the pole stage's images are the panorama extended to this many widths, x % cols
@@ -178,6 +192,9 @@ void frame_composite(s360_ctx* c, int pole_mask);
 void frame_render_batch(s360_ctx* c, int use_prev);
 void frame_render_slots(s360_ctx* c, const int* slots, int n, int use_prev);  // ... a subset of them (ascending, distinct)
 void set_frame_slots(s360_ctx* c, int n);
+// The context's frame JPEG encoder (s360_set_jpeg_encode), created on first use and grown to `mcus` MCUs of 16 x 16 pixels; its
+// tables are those of the context's quality when this returns. Waits for the device when it has to build or rebuild anything.
+JpegEncoder& frame_jpeg_encoder(s360_ctx* c, long long mcus, hipStream_t st);
 // stereo cubemap of the last finished frame into F.cubeOut; returns its width/height through ow/oh
 void frame_cubemap(s360_ctx* c, int face_w, int face_h, bool video, int* ow, int* oh);
 // the context's face maps for (face size, eye size), with their prepared form for `video` (0 / 1) when video >= 0: built on

@@ -895,6 +895,62 @@ class Context:
             self._ck(lib().s360_frame_download_cubemap_png_slot(self.h, int(slot), int(age), _p(out), C.c_size_t(out.size), C.byref(n)))
         return out[:n.value]
 
+    # ---- the equirect and the cubemap as JPEG files, encoded on the device (include/s360_frame_jpeg.h) ----
+    def set_jpeg_encode(self, on=True, quality=95):
+        """Frames enqueued from now on are also encoded as baseline JPEG (quality 1..100, clamped); independent of set_png_encode."""
+        self._ck(lib().s360_set_jpeg_encode(self.h, int(bool(on)), int(quality)))
+
+    def jpeg_bound(self):
+        return int(lib().s360_frame_jpeg_bound(self.h))
+
+    def cubemap_jpeg_bound(self):
+        return int(lib().s360_frame_cubemap_jpeg_bound(self.h))
+
+    def _download_jpeg(self, stem, bound, age, slot, out):
+        if out is None:
+            out = np.empty(max(bound, 1), np.uint8)
+        assert out.dtype == np.uint8 and out.ndim == 1 and out.flags["C_CONTIGUOUS"]
+        n = C.c_size_t(0)
+        if slot is None:
+            rc = getattr(lib(), stem)(self.h, int(age), _p(out), C.c_size_t(out.size), C.byref(n))
+        else:
+            rc = getattr(lib(), stem + "_slot")(self.h, int(slot), int(age), _p(out), C.c_size_t(out.size), C.byref(n))
+        self.jpeg_size_needed = n.value  # (what a refused call says the file needs)
+        self._ck(rc)
+        return out[:n.value]
+
+    def download_jpeg(self, age=0, out=None):
+        """The finished frame as the bytes of a complete JPEG file (rendered with set_jpeg_encode(True)): jpegio::encode of the
+        pixels download_equirect_of returns. `out`: a uint8 buffer, jpeg_bound() bytes hold every file (pinned_empty: one DMA
+        transfer); returns a view of the file's bytes in it."""
+        return self._download_jpeg("s360_frame_download_jpeg", self.jpeg_bound(), age, None, out)
+
+    def download_jpeg_slot(self, slot, age=0, out=None):
+        return self._download_jpeg("s360_frame_download_jpeg", self.jpeg_bound(), age, slot, out)
+
+    def download_cubemap_jpeg(self, age=0, out=None):
+        """The frame's cubemap (set_cubemap_output) as the bytes of a complete JPEG file."""
+        return self._download_jpeg("s360_frame_download_cubemap_jpeg", self.cubemap_jpeg_bound(), age, None, out)
+
+    def download_cubemap_jpeg_slot(self, slot, age=0, out=None):
+        return self._download_jpeg("s360_frame_download_cubemap_jpeg", self.cubemap_jpeg_bound(), age, slot, out)
+
+    def debug_frame_jpeg(self, bgr, scan_cap, cap=None):
+        """include/s360_debug_frame_jpeg.h: `bgr` through the context's frame encoder into a device buffer of scan_cap bytes.
+        Returns (file bytes or None, dict(rc, message, n_out, stored, guard_touched, ms))."""
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        h, w = bgr.shape[:2]
+        if cap is None:
+            cap = 623 + int(scan_cap) + 2
+        out = np.empty(max(int(cap), 1), np.uint8)
+        n, stored, guard = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        ms = C.c_float(0)
+        rc = lib().s360_debug_frame_jpeg(self.h, _p(bgr), w, h, C.c_size_t(int(scan_cap)), _p(out), C.c_size_t(int(cap)), C.byref(n),
+                                         C.byref(stored), C.byref(guard), C.byref(ms))
+        msg = lib().s360_last_error(self.h) if rc < 0 else b""
+        info = dict(rc=rc, message=msg.decode() if msg else "", n_out=n.value, stored=stored.value, guard_touched=guard.value, ms=ms.value)
+        return (out[:n.value].tobytes() if rc == 0 else None), info
+
     def set_sharpening(self, sharpening):
         """FLAGS_sharpening for the frames rendered from now on (TRSP:56, :901)."""
         self._ck(lib().s360_set_sharpening(self.h, C.c_double(sharpening)))
