@@ -5,7 +5,8 @@
 //
 // Kept on the host, as in the reference: flag parsing, the rig loader (inside libs360: rig.cpp), directory
 // scanning, PNG decode/encode (png_io.hpp instead of cv::imread/imwrite) and the flow-state files.
-// Not supported here: --save_debug_images (debug PNGs only).
+// --save_debug_images writes the reference's debug images under <output_data_dir>/debug/<frame>/ (write_debug_images below): one
+// frame per process or --num_frames, on one GPU.
 // Opt-in additions: --num_gpus G (one frame sharded over G GPUs, native RCCL strip gather) and --num_frames N (a
 // stream of N consecutive frames in one process: device-resident temporal state, overlapped I/O).
 #include <dirent.h>
@@ -1035,6 +1036,62 @@ void write_state(const Job& J, const std::string& frame) {
   g_stateTimes.writers += now_sec() - t00 - tImages - tFlows;
 }
 
+// --save_debug_images: the reference's files under <output_data_dir>/debug/<frame>/ (TRSP:177-184, 548-560, 639-643, 680-684,
+// 792-801, 896-911; PoleRemoval.cpp:148-153, 185-187), names and order from the library (include/s360_debug_images.h). The frame
+// was rendered with s360_set_debug_images on. Directories are the caller's (batch_process_video.py:132-135): a missing one is the
+// write error it is in the reference. Old projections/* files are removed first (TRSP:766-770). Default: the images' pixels come
+// back raw and the pool of write_state's kind encodes them (png_io.hpp); --device_state_png (or its environment switch): they are
+// encoded where they lie, ONE batched launch sequence for all of them (s360_frame_encode_debug_pngs), and the pool only writes bytes.
+struct DebugTimes { int files = 0; size_t bytes = 0; double seconds = 0; bool device = false; };
+DebugTimes g_debugTimes;
+void write_debug_images(const Job& J, const std::string& frame) {
+  const double t0 = now_sec();
+  s360_ctx* c = J.ctx[0];
+  const std::string debugDir = J.F.s("output_data_dir") + "/debug/" + frame;
+  const std::string projDir = debugDir + "/projections";
+  if (DIR* d = opendir(projDir.c_str())) {  // rm -f projections/*
+    std::vector<std::string> old;
+    while (dirent* e = readdir(d))
+      if (std::strcmp(e->d_name, ".") && std::strcmp(e->d_name, "..")) old.push_back(e->d_name);
+    closedir(d);
+    for (const std::string& n : old) (void)unlink((projDir + "/" + n).c_str());
+  }
+  const int n = s360_frame_debug_image_count(c);
+  ck(n, c);
+  const bool dev = device_state_png(J.F);
+  if (dev) ck(s360_frame_encode_debug_pngs(c), c);
+  std::atomic<size_t> bytes(0);
+  {
+    TaskQueue coders(state_workers());  // (joined at the end of this block: every file is complete then)
+    for (int i = 0; i < n; ++i) {
+      char name[96];
+      int whc[3];
+      ck(s360_frame_debug_image_info(c, i, name, whc), c);
+      const std::string path = debugDir + "/" + name;
+      if (dev) {
+        const size_t cap = s360_frame_debug_png_bound(c, i);
+        std::shared_ptr<uint8_t> file(new uint8_t[cap], std::default_delete<uint8_t[]>());
+        size_t nb = 0;
+        ck(s360_frame_download_debug_png(c, i, file.get(), cap, &nb), c);
+        coders.push([path, file, nb, &bytes] { save_bytes(path, file.get(), nb); bytes += nb; });
+      } else {
+        auto px = std::make_shared<std::vector<uint8_t>>((size_t)whc[0] * whc[1] * whc[2]);
+        ck(s360_frame_get_debug_image(c, i, px->data()), c);
+        const int w = whc[0], h = whc[1], ch = whc[2];
+        coders.push([path, px, w, h, ch, &bytes] {
+          save_png(path, px->data(), w, h, ch);
+          struct stat st;
+          if (stat(path.c_str(), &st) == 0) bytes += (size_t)st.st_size;
+        });
+      }
+    }
+  }
+  g_debugTimes.files += n;
+  g_debugTimes.bytes += bytes.load();
+  g_debugTimes.seconds += now_sec() - t0;
+  g_debugTimes.device = dev;
+}
+
 // "000123" + 1 -> "000124" (same width); frame names of the reference's datasets are zero-padded decimal numbers
 std::string next_frame_name(const std::string& f) {
   char buf[64];
@@ -1186,7 +1243,11 @@ static int run_job(const Flags& flags) {
     if (s360_comm_init_all(J.ctx.data(), G) < 0) die(s360_last_error(nullptr));
     for (int r = 0; r < G; ++r) ck(s360_frame_set_partition(J.ctx[r], J.bounds[r], J.bounds[r + 1]), J.ctx[r]);
   }
-  if (numFrames > 1) {
+  // --save_debug_images: every frame keeps the reference's debug images until they are written, so the frames of a stream are
+  // rendered one at a time — no frame pipelining, frame k + 1 is enqueued when frame k's files are out (main refuses several GPUs)
+  const bool debugImages = F.b("save_debug_images");
+  if (debugImages) ck(s360_set_debug_images(J.ctx[0], 1), J.ctx[0]);
+  if (numFrames > 1 && !debugImages) {
     ck(s360_set_frame_pipelining(J.ctx[0], 1), J.ctx[0]);  // pole stage of frame k overlaps side stage of k+1
   }
   if (!F.s("bin_list").empty()) open_bins(J);
@@ -1272,7 +1333,7 @@ static int run_job(const Flags& flags) {
     if (k == 3 && numFrames > 4) { tDecode = tUpload = tFetch = tJoin = 0; tSteadyStart = now_sec(); }
     if (k >= 3) ++steadyFrames;
     std::string nextName;
-    if (!last) {  // feed frame k+1 behind frame k: the GPU never waits for the host
+    auto feed_next = [&] {  // frame k+1
       nextName = next_frame_name(frame);
       const double t0 = now_sec();
       FrameInputs nin = decoding.front().get();
@@ -1284,13 +1345,15 @@ static int run_job(const Flags& flags) {
       leaving.push_back(std::move(nin));  // (sent in place: recycled once the uploads have run, below)
       tDecode += t1 - t0;
       tUpload += now_sec() - t1;
-    }
+    };
+    if (!last && !debugImages) feed_next();  // behind frame k: the GPU never waits for the host
     const double tf = now_sec();
     size_t pngBytes = 0;
+    const int age = last || debugImages ? 0 : 1;  // the latest enqueued frame is k+1, except at the end and with --save_debug_images
     if (!is_file(eqMode) && last) ck(s360_frame_download_equirect(J.ctx[0], outBuf[cur].data()), J.ctx[0]);
-    else fetch_output(J.ctx[0], eqMode, false, -1, last ? 0 : 1, outBuf[cur].data(), outBuf[cur].size(), &pngBytes);  // frame k, while k+1 renders
+    else fetch_output(J.ctx[0], eqMode, false, -1, age, outBuf[cur].data(), outBuf[cur].size(), &pngBytes);  // frame k, while k+1 renders
     size_t cubePngBytes = 0;
-    if (cubeStream) fetch_output(J.ctx[0], cmMode, true, -1, last ? 0 : 1, cubeBuf[cur].data(), cubeBuf[cur].size(), &cubePngBytes);
+    if (cubeStream) fetch_output(J.ctx[0], cmMode, true, -1, age, cubeBuf[cur].data(), cubeBuf[cur].size(), &cubePngBytes);
     if (!leaving.empty()) {  // frame k is complete, so frame k+1's uploads (enqueued before it rendered) are long done
       ck(s360_frame_uploads_complete(J.ctx[0]), J.ctx[0]);
       for (auto& fi : leaving) spare.push_back(std::move(fi));
@@ -1312,6 +1375,7 @@ static int run_job(const Flags& flags) {
     // the reference writes the state of every frame; a stream only needs it to resume after its last frame. (Beside the
     // equirect's encoder, not in front of it.)
     if (F.b("write_state") && last) write_state(J, frame);
+    if (debugImages) write_debug_images(J, frame);
     stateEnd = now_sec();
     if (last && cube && !cubeStream) {  // optional stereo cubemap (TRSP:917-935)
       int whc[3];
@@ -1328,6 +1392,7 @@ static int run_job(const Flags& flags) {
       for (auto& e : encoder)
         if (e.joinable()) e.join();
     tJoin += now_sec() - tj;
+    if (!last && debugImages) feed_next();  // frame k's debug images are out: the next render may overwrite them
     frame = nextName;
   }
   const double endTime = now_sec();
@@ -1358,6 +1423,9 @@ static int run_job(const Flags& flags) {
                    numFrames - nf, numFrames - 1);
     }
     report_input_paths(F);
+    if (debugImages)
+      std::fprintf(stderr, "debug images:            %d files, %.1f MB, %.3f  (%s)\n", g_debugTimes.files, g_debugTimes.bytes / 1e6, g_debugTimes.seconds,
+                   g_debugTimes.device ? "encoded on the device in one batch per frame, written as bytes" : "fetched raw, encoded by the writers");
     std::fprintf(stderr, "TOTAL:                   %.3f\n", endTime - startTime);
   }
   if (g_fast_exit) return 0;  // main leaves the process at once (one frame per process): the device memory goes with it
@@ -1579,6 +1647,8 @@ int main(int argc, char** argv) {
   Flags F;
   F.parse(argc, argv);
   const int streams = std::max(1, F.i("num_streams")), frames = std::max(1, F.i("num_frames"));
+  if (F.b("save_debug_images") && (streams > 1 || F.i("num_gpus") > 1))  // (before any GPU work)
+    Flags::fail("--save_debug_images is not available with --num_streams or --num_gpus above 1: the images of one frame live on several contexts");
   if (frames > 1 && F.i("cubemap_width") > 0 && F.i("cubemap_height") > 0 && !F.s("output_cubemap_path").empty() &&
       frame_path(F.s("output_cubemap_path"), "0") == frame_path(F.s("output_cubemap_path"), "1"))
     die("--output_cubemap_path must contain %s or {frame} with --num_frames > 1: " + std::to_string(frames) +

@@ -537,4 +537,5 @@ int s360_isp_config_tables(const s360_isp_config* cfg, float* ccm9, float* lut, 
 #include "s360_input_png.h" /* ... and those camera files decoded on the device into a frame's source slots */
 #include "s360_input_jpeg.h" /* ... and camera files that are baseline JPEGs, decoded on the device the same way */
 #include "s360_frame_jpeg.h" /* the finished frame as a JPEG file, encoded on the device: a .jpg output path */
+#include "s360_debug_images.h" /* the reference's --save_debug_images files of a frame; pole removal as an operator */
 #endif /* S360_H_ */

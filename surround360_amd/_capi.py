@@ -116,6 +116,12 @@ FRAME_JPEG_SYMBOLS = ("s360_set_jpeg_encode", "s360_frame_jpeg_bound", "s360_fra
                       "s360_frame_download_jpeg_slot", "s360_frame_download_cubemap_jpeg", "s360_frame_download_cubemap_jpeg_slot")
 # ... and its test tap, include/s360_debug_frame_jpeg.h
 DEBUG_FRAME_JPEG_SYMBOLS = ("s360_debug_frame_jpeg",)
+# ... and every symbol include/s360_debug_images.h declares (the reference's debug images of a frame; pole removal as an operator)
+DEBUG_IMAGES_SYMBOLS = ("s360_set_debug_images", "s360_frame_debug_image_count", "s360_frame_debug_image_info", "s360_frame_get_debug_image",
+                        "s360_frame_encode_debug_pngs", "s360_frame_debug_png_bound", "s360_frame_download_debug_png",
+                        "s360_pole_removal_combine")
+# ... and its test tap, include/s360_debug_views.h
+DEBUG_VIEWS_SYMBOLS = ("s360_debug_views",)
 # ... and the test taps include/s360_debug.h declares (not part of the API)
 DEBUG_SYMBOLS = ["s360_debug_entry_downscale"]
 # ... and the one include/s360_debug_final_flow.h declares
@@ -144,6 +150,12 @@ DEBUG_PREVIEW_SYMBOLS = ["s360_debug_preview_camera", "s360_debug_preview_map", 
 JPEG_SYMBOLS = ["s360_jpeg_create", "s360_jpeg_destroy", "s360_jpeg_bound", "s360_jpeg_encode", "s360_jpeg_last_time"]
 # ... and its test tap, include/s360_debug_jpeg.h
 DEBUG_JPEG_SYMBOLS = ["s360_debug_jpeg_blocks"]
+
+
+class DebugView(C.Structure):
+    """s360_debug_view (include/s360_debug_views.h)."""
+    _fields_ = [("src_off", C.c_uint64), ("dst_off", C.c_uint64)] + \
+               [(n, C.c_int32) for n in ("src_pitch", "src_rows", "x0", "y0", "w", "h", "shift", "pad_rows", "channels_in", "channels_out")]
 
 
 class FlowPrepareOut(C.Structure):
@@ -261,6 +273,25 @@ def lib():
         L.s360_debug_frame_jpeg.restype = C.c_int
         L.s360_debug_frame_jpeg.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t] + \
                                            [C.POINTER(C.c_size_t)] * 3 + [C.POINTER(C.c_float)]
+        L.s360_set_debug_images.restype = C.c_int
+        L.s360_set_debug_images.argtypes = [C.c_void_p, C.c_int]
+        L.s360_frame_debug_image_count.restype = C.c_int
+        L.s360_frame_debug_image_count.argtypes = [C.c_void_p]
+        L.s360_frame_debug_image_info.restype = C.c_int
+        L.s360_frame_debug_image_info.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]
+        L.s360_frame_get_debug_image.restype = C.c_int
+        L.s360_frame_get_debug_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.s360_frame_encode_debug_pngs.restype = C.c_int
+        L.s360_frame_encode_debug_pngs.argtypes = [C.c_void_p]
+        L.s360_frame_debug_png_bound.restype = C.c_size_t
+        L.s360_frame_debug_png_bound.argtypes = [C.c_void_p, C.c_int]
+        L.s360_frame_download_debug_png.restype = C.c_int
+        L.s360_frame_download_debug_png.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.s360_pole_removal_combine.restype = C.c_int
+        L.s360_pole_removal_combine.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int,
+                                                                                C.c_char_p] + [C.c_void_p] * 5
+        L.s360_debug_views.restype = C.c_int
+        L.s360_debug_views.argtypes = [C.c_void_p, C.c_int, C.POINTER(DebugView), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         L.s360_debug_isp_stages.restype = C.c_int
         L.s360_debug_isp_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8
         L.s360_debug_flow_level.restype = C.c_int

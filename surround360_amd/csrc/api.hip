@@ -330,7 +330,7 @@ void s360_destroy(s360_ctx* c) {
       if (e->ready) (void)hipEventDestroy(e->ready);
   if (c->evMaps) (void)hipEventDestroy(c->evMaps);
   if (c->evDown) (void)hipEventDestroy(c->evDown);
-  for (s360_ctx::PngBatch* B : {&c->statePng, &c->opPng})
+  for (s360_ctx::PngBatch* B : {&c->statePng, &c->opPng, &c->debugPng})
     if (B->events) { (void)hipEventDestroy(B->evEnc); (void)hipEventDestroy(B->evRead); (void)hipEventDestroy(B->evAfter); }
   if (c->evUpHost) (void)hipEventDestroy(c->evUpHost);
   if (c->stUp) {
@@ -362,6 +362,7 @@ int s360_synchronize(s360_ctx* c) {
 int s360_set_frame_pipelining(s360_ctx* c, int on) {
   return guard(c, [&] {
     need(c, "null ctx");
+    if (on && c->debug_images) throw Error(S360_ERR_STATE, "frame pipelining is not available while s360_set_debug_images is on (frames are rendered one at a time)");
     c->make_current();
     S360_HIP(hipStreamSynchronize(c->st));
     if (c->st2) S360_HIP(hipStreamSynchronize(c->st2));

@@ -1,7 +1,9 @@
 // api_internal.hpp — the few helpers that the files of the C ABI share (api.hip, api_ops.hip, api_png.hip, api_taps.hip,
 // api_isp.hip), besides the guard (api_guard.hpp).
 #pragma once
+#include <mutex>
 #include <string>
+#include <vector>
 
 #include "api_guard.hpp"
 #include "ctx.hpp"
@@ -31,6 +33,14 @@ FrameState& slot_state(s360_ctx* c, int slot);
 void ensure_download_stream(s360_ctx* c);
 int frame_buffer(s360_ctx* c, FrameState& F, int age);
 int cube_buffer(s360_ctx* c, FrameState& F, int age);
+
+// api_png.hip: a batch of PNG files encoded by one launch sequence (ctx.hpp PngBatch): its plan and page-locked areas; its launch
+// sequence over the device images px[i] on the context's stream, the band tables' copy behind it (nothing waits); file i of the
+// batch into the caller's buffer (`release`: the context is given back while the call waits and while it computes the CRCs)
+void png_batch_prepare(s360_ctx* c, s360_ctx::PngBatch& B, const std::vector<PngPlan>& plans);
+void png_batch_run(s360_ctx* c, s360_ctx::PngBatch& B, const uint8_t* const* px);
+void png_batch_fetch(s360_ctx* c, std::unique_lock<std::recursive_mutex>& lk, s360_ctx::PngBatch& B, int i, uint8_t* out, size_t cap,
+                     size_t* n_out, bool release);
 
 inline void h2d(s360_ctx* c, void* d, const void* h, size_t n) {
   S360_HIP(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, c->st));

@@ -220,9 +220,11 @@ size_t s360_png_bound_c(int w, int h, int channels) { return png_file_bound(w, h
 int s360_encode_png_c(s360_ctx* c, const uint8_t* px, int w, int h, int channels, uint8_t* out, size_t cap, size_t* n_out) {
   return encode_png_op(c, px, w, h, channels, 8, nullptr, false, out, cap, n_out);
 }
+}  // extern "C"
+namespace s360 {
 // A batch's plan and its page-locked areas. The table's host copy is rewritten here: the upload of the batch before (a whole encode
 // ago) has left it in any real use; if it has not, this is the one place that waits for it.
-static void png_batch_prepare(s360_ctx* c, s360_ctx::PngBatch& B, const std::vector<PngPlan>& plans) {
+void png_batch_prepare(s360_ctx* c, s360_ctx::PngBatch& B, const std::vector<PngPlan>& plans) {
   if (!B.events) {
     S360_HIP(hipEventCreateWithFlags(&B.evEnc, hipEventDisableTiming));
     S360_HIP(hipEventCreateWithFlags(&B.evRead, hipEventDisableTiming));
@@ -239,7 +241,7 @@ static void png_batch_prepare(s360_ctx* c, s360_ctx::PngBatch& B, const std::vec
   B.metaHost.ensure(B.plan.meta_records * sizeof(PngBandMeta));
 }
 // ... and its launch sequence on the context's stream, the band tables' copy to the host behind it. Nothing waits.
-static void png_batch_run(s360_ctx* c, s360_ctx::PngBatch& B, const uint8_t* const* px) {
+void png_batch_run(s360_ctx* c, s360_ctx::PngBatch& B, const uint8_t* const* px) {
   if (B.haveRead) S360_HIP(hipStreamWaitEvent(c->st, B.evRead, 0));  // (a fetch of the batch before may still read its file images)
   png_batch_enqueue(c->st, px, B.plan, B.table, B.tabHost.p, B.scratch, B.meta, B.files);
   S360_HIP(hipMemcpyAsync(B.metaHost.p, B.meta.p, B.plan.meta_records * sizeof(PngBandMeta), hipMemcpyDeviceToHost, c->st));
@@ -251,7 +253,7 @@ static void png_batch_run(s360_ctx* c, s360_ctx::PngBatch& B, const uint8_t* con
 // the lock is first released; plan, pointers and the batch's generation are taken by value. The file's size is known up front when
 // the band tables have already arrived (the usual case from the second file on); otherwise as much as the caller's buffer or the
 // file's bound allows is copied, and the size is checked afterwards — a buffer that turns out too small is refused, never overrun.
-static void png_batch_fetch(s360_ctx* c, std::unique_lock<std::recursive_mutex>& lk, s360_ctx::PngBatch& B, int i, uint8_t* out, size_t cap,
+void png_batch_fetch(s360_ctx* c, std::unique_lock<std::recursive_mutex>& lk, s360_ctx::PngBatch& B, int i, uint8_t* out, size_t cap,
                             size_t* n_out, bool release) {
   if (!B.haveEnc) throw Error(S360_ERR_STATE, "no PNG batch has been encoded");
   need(i >= 0 && (size_t)i < B.plan.img.size(), "PNG index out of range");
@@ -295,6 +297,8 @@ static void png_batch_fetch(s360_ctx* c, std::unique_lock<std::recursive_mutex>&
   if (release) lk.lock();
   *n_out = n;
 }
+}  // namespace s360
+extern "C" {
 int s360_encode_png_batch(s360_ctx* c, int n, const uint8_t* const* px, const int* w, const int* h, const int* channels, uint8_t* const* out,
                           const size_t* cap, size_t* n_out) {
   if (!c) return S360_ERR_INVALID_ARG;

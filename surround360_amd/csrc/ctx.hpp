@@ -69,6 +69,10 @@ struct s360_ctx {
     unsigned long long gen = 0;
   };
   PngBatch statePng, opPng;
+  // s360_set_debug_images (include/s360_debug_images.h): frames are rendered one at a time and keep the reference's debug images
+  // (render.hpp FrameState::DebugImages); their files are a batch of their own (s360_frame_encode_debug_pngs -> debugPng)
+  bool debug_images = false;
+  PngBatch debugPng;
   // the PNG decoder (png_decode.hip): its buffers (grow only) and the counters of the last decode call on this context
   s360::PngDecodeBufs pngDec;
   unsigned long long pngDecStats[s360::kPngDecodeStatWords] = {0};

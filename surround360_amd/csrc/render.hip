@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
@@ -224,11 +225,24 @@ FlowEngine& flow_engine(s360_ctx* c, int which) {
 }
 void set_frame_slots(s360_ctx* c, int n) {
   if (n < 1 || n > 64) throw Error(S360_ERR_INVALID_ARG, "frame slots must be 1..64");
+  if (n > 1 && c->debug_images) throw Error(S360_ERR_STATE, "one frame slot while s360_set_debug_images is on (frames are rendered one at a time)");
   S360_HIP(hipStreamSynchronize(c->st));
   if (c->st2) S360_HIP(hipStreamSynchronize(c->st2));
   if (c->stUp) S360_HIP(hipStreamSynchronize(c->stUp));
   c->slots.resize(n);
   if (c->slot >= n) c->slot = 0;
+}
+void set_debug_images(s360_ctx* c, bool on) {
+  if (on && c->slots.size() > 1) throw Error(S360_ERR_STATE, "debug images need a context with one frame slot (frames are rendered one at a time)");
+  S360_HIP(hipStreamSynchronize(c->st));
+  if (c->st2) S360_HIP(hipStreamSynchronize(c->st2));
+  if (on && c->pipeline) {
+    c->pipeline = false;
+    c->haveStripsFree = false;
+    flow_engines_follow_pipelining(c);
+  }
+  c->debug_images = on;
+  if (!on) frame_state(c).dbg.frame = -1;
 }
 namespace {
 struct SlotScope {  // the helpers below find their scratch buffers through frame_state(c): select the slot they work on
@@ -842,6 +856,90 @@ void frame_jpeg_enqueue(s360_ctx* c, FrameState& F, int ob, int k, const uint8_t
 // of the layers of `composite_mask` (computed here or received: frame_gather_pole_layers) + sharpen / resize / stack.
 // s360_frame_finish is both phases with the same mask; a frame whose pole units are spread over GPUs
 // runs phase 1 on every owner and phase 2 on the root.
+// s360_set_debug_images: the list of the reference's --save_debug_images files for the frame `F` has just composited (its finish
+// stage is about to record outDone), and the ONE k_debug_views launch for those no buffer holds as written. Order and names:
+// include/s360_debug_images.h. Pole unit u appears when this context computed its layer for this frame.
+static void debug_images_collect(s360_ctx* c, FrameState& F, int composite_mask, hipStream_t st) {
+  const s360_geometry& g = c->g;
+  const int W = c->P.eqr_width, H = c->P.eqr_height, P = F.P, camW = g.cam_image_width, camH = g.cam_image_height;
+  const PrevLayout L(c, F.side_p0, F.side_p1);
+  static const char* const kEye[4] = {"top_left", "top_right", "bottom_left", "bottom_right"};
+  FrameState::DebugImages& D = F.dbg;
+  D.list.clear();
+  D.frame = -1;
+  std::vector<DebugViewDesc> views;
+  std::vector<size_t> viewImg;  // views[k] is written for list[viewImg[k]]
+  size_t viewBytes = 0;
+  auto add = [&](const std::string& name, int w, int h, int ch, const void* px) {
+    FrameState::DebugImages::Img m;
+    std::snprintf(m.name, sizeof m.name, "%s", name.c_str());
+    m.w = w; m.h = h; m.ch = ch; m.px = static_cast<const uint8_t*>(px);
+    D.list.push_back(m);
+  };
+  // a view of `src` (pitch x rows pixels): rectangle, shift, channels out; its pixels are placed in D.views below
+  auto add_view = [&](const std::string& name, const void* src, int pitch, int rows, int x0, int y0, int w, int h, int shift, int cout) {
+    DebugViewDesc d{};
+    d.src = static_cast<const uint8_t*>(src); d.dst = nullptr; d.src_pitch = pitch; d.src_rows = rows;
+    d.x0 = x0; d.y0 = y0; d.w = w; d.h = h; d.shift = shift; d.pad_rows = 0; d.channels_in = 4; d.channels_out = cout;
+    views.push_back(d);
+    viewImg.push_back(D.list.size());
+    add(name, w, h, cout, reinterpret_cast<const void*>(viewBytes));  // (an offset until D.views is sized)
+    viewBytes += ((size_t)w * h * cout + 255) & ~(size_t)255;
+  };
+  if (F.sc->proj.p && F.side_p0 == 0 && F.side_p1 == P)
+    for (int i = 0; i < P; ++i)
+      add(std::string("projections/crop_") + c->rig.side[(size_t)i].id + ".png", camW, camH, 4,
+          F.sc->proj.as<uchar4>() + (size_t)camW * camH * i);
+  if (F.panoDbg[0].p && F.panoDbg[1].p && camH <= H) {
+    const int padAbove = (H - camH) / 2;  // padToheight (TRSP:701-713)
+    for (int e = 0; e < 2; ++e) add(e ? "sphericalImgR.png" : "sphericalImgL.png", W, camH, 4, F.panoDbg[e].as<uchar4>() + (size_t)W * padAbove);
+    for (int e = 0; e < 2; ++e)
+      add_view(e ? "sphericalImg_offsetwrapR.png" : "sphericalImg_offsetwrapL.png", F.panoDbg[e].p, W, H, 0, padAbove, W, camH, W / 3, 4);
+  }
+  bool unit[4];
+  for (int u = 0; u < 4; ++u)
+    unit[u] = (composite_mask & (1 << u)) && F.sc->poleWarped[u].p && F.poleFrame[u] == F.frames_done && F.sc->poleOwner[u] == &F &&
+              F.extImgs[F.last_pole].p && L.rows(u) <= H;
+  if ((unit[0] || unit[1]) && F.sc->topSph.p) add("_topSpherical.png", W, L.rowsT, 4, F.sc->topSph.p);
+  if (unit[2] || unit[3]) {
+    if (c->P.enable_pole_removal && F.have_prev_pr && F.prImgs[F.last_pr].p && F.prWarp.p && F.prMerged.p) {
+      const size_t n = (size_t)F.poleW * F.poleH;
+      add("bottomImage.png", F.poleW, F.poleH, 4, F.prImgs[F.last_pr].p);
+      add("bottomImage2.png", F.poleW, F.poleH, 4, F.prImgs[F.last_pr].as<uchar4>() + n);
+      add("bottomWarp2.png", F.poleW, F.poleH, 4, F.prWarp.p);
+      add("_bottomCombined.png", F.poleW, F.poleH, 4, F.prMerged.p);
+    }
+    if (F.sc->botSph.p) add("_bottomSpherical.png", W, L.rowsB, 4, F.sc->botSph.p);
+  }
+  for (int u = 0; u < 4; ++u) {
+    if (!unit[u]) continue;
+    const uchar4* extSide = F.extImgs[F.last_pole].as<uchar4>() + L.side(u);
+    add_view(std::string("croppedSideSpherical_") + kEye[u] + ".png", extSide, L.extW, L.rows(u), 0, 0, W, L.rows(u), 0, 4);
+    add(std::string("warpedSpherical_") + kEye[u] + ".png", W, H, 4, F.sc->poleWarped[u].p);  // (the rows below the layer are kept zeroed)
+    add(std::string("extendedSideSpherical_") + kEye[u] + ".png", L.extW, L.rows(u), 4, extSide);
+  }
+  const bool sharpened = c->P.sharpening > 0.0;
+  for (int e = 0; e < 2; ++e)
+    add_view(e ? "eqr_sideR.png" : "eqr_sideL.png", sharpened ? F.dbg.eyeKeep[e].p : F.pano[e].p, W, H, 0, 0, W, H, 0, 3);
+  if (sharpened)
+    for (int e = 0; e < 2; ++e) add_view(e ? "_eqr_sideR_sharpened.png" : "_eqr_sideL_sharpened.png", F.pano[e].p, W, H, 0, 0, W, H, 0, 3);
+  D.views.ensure(viewBytes);
+  D.table.ensure(views.size() * sizeof(DebugViewDesc));
+  D.tableHost.ensure(views.size() * sizeof(DebugViewDesc));
+  for (size_t k = 0; k < views.size(); ++k) {
+    FrameState::DebugImages::Img& m = D.list[viewImg[k]];
+    m.px = D.views.as<uint8_t>() + reinterpret_cast<size_t>(m.px);
+    views[k].dst = const_cast<uint8_t*>(m.px);
+  }
+  std::memcpy(D.tableHost.p, views.data(), views.size() * sizeof(DebugViewDesc));
+  {
+    ProfScope ps(c->prof, "debug_views");
+    S360_HIP(hipMemcpyAsync(D.table.p, D.tableHost.p, views.size() * sizeof(DebugViewDesc), hipMemcpyHostToDevice, st));
+    launch_debug_views(st, D.table.as<DebugViewDesc>(), D.tableHost.as<DebugViewDesc>(), (int)views.size());
+  }
+  D.frame = F.frames_done;
+}
+
 static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_mask, int use_prev, int phases = 3,
                          int composite_mask = -1) {
   if (composite_mask < 0) composite_mask = pole_mask;
@@ -885,7 +983,7 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
       launch_assemble_pano(st, F.strips.as<uchar4>() + (size_t)P * camH * stripW, P, camH, stripW, -sh,
                            F.pano[1].as<uchar4>(), W, H);
     }
-    if (F.keep_intermediates)
+    if (F.keep_intermediates || c->debug_images)  // (sphericalImg{L,R}.png are the camera rows of these copies)
       for (int e = 0; e < 2; ++e) {
         F.panoDbg[e].ensure(en * sizeof(uchar4));
         S360_HIP(hipMemcpyAsync(F.panoDbg[e].p, F.pano[e].p, en * sizeof(uchar4), hipMemcpyDeviceToDevice, st));
@@ -1060,6 +1158,15 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
     }
   }
   if (!(phases & 2)) return;
+  if (c->debug_images && c->P.sharpening > 0.0)  // eqr_side{L,R}.png (TRSP:896-899): the sharpen below works in place
+    for (int k : slotIds) {
+      SlotScope ss(c, k);
+      FrameState& F = frame_state(c);
+      for (int e = 0; e < 2; ++e) {
+        F.dbg.eyeKeep[e].ensure(en * sizeof(uchar4));
+        S360_HIP(hipMemcpyAsync(F.dbg.eyeKeep[e].p, F.pano[e].p, en * sizeof(uchar4), hipMemcpyDeviceToDevice, st));
+      }
+    }
   // sharpenThread for the eyes of several slots per set of launches (TRSP:901-915 runs the two eyes on two threads): the
   // IIR passes are one serial chain per (row, channel) — the 2 x 4096 rows of one frame are 512 waves, half a wave per
   // SIMD — so the slots of a batch are sharpened in groups of SlotScratch::kSharpenGroup images (several waves per SIMD
@@ -1173,11 +1280,15 @@ static void finish_stage(s360_ctx* c, const std::vector<int>& slotIds, int pole_
           }
         }
       }
+      if (c->debug_images) debug_images_collect(c, F, composite_mask, st);
+      else F.dbg.frame = -1;
       S360_HIP(hipEventRecord(F.outDone[ob], st));
       F.out_cur = ob;
       ++F.frames_done;
     }
   }
+  // debug images: frames are rendered one at a time (the kept images and their table are the slot's, not the frame's)
+  if (c->debug_images) S360_HIP(hipStreamSynchronize(st));
 }
 void frame_finish(s360_ctx* c, int pole_mask, int use_prev) { finish_stage(c, {c->slot}, pole_mask, use_prev); }
 void frame_pole_units(s360_ctx* c, int pole_mask, int use_prev) { finish_stage(c, {c->slot}, pole_mask, use_prev, 1, 0); }

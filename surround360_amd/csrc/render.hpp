@@ -7,6 +7,7 @@
 
 #include "core.hpp"
 #include "ctx.hpp"
+#include "debug_views.hpp"
 #include "png.hpp"
 #include "render_kernels.hpp"
 
@@ -137,6 +138,19 @@ struct FrameState {
   } jpeg[2];
   DevBuf jpegCount[2];
   PinBuf jpegCountPin[2];
+  // s360_set_debug_images (include/s360_debug_images.h): what the reference's --save_debug_images files of this slot's latest frame
+  // are read from. Most of them are buffers the frame leaves behind anyway (projections, pole projections, warped layers, extended
+  // side images, pole removal's images: `list` points at them); kept apart are the panoramas before the pole composite (panoDbg,
+  // shared with keep_intermediates) and, with sharpening, the eyes before the sharpen overwrites them (eyeKeep); `views` holds what
+  // ONE k_debug_views launch behind the frame's last kernel writes through `table`: the cropped feathered side images, the
+  // offset-wrapped panoramas, the eyes without alpha. Nothing of this is allocated while the switch has never been on.
+  struct DebugImages {
+    struct Img { char name[96]; int w, h, ch; const uint8_t* px; };
+    std::vector<Img> list;  // in the order of include/s360_debug_images.h
+    long long frame = -1;   // the frame (frames_done at its finish stage) the list describes; -1: none
+    DevBuf eyeKeep[2], views, table;
+    PinBuf tableHost;
+  } dbg;
 };
 
 // kExtendFrac (TRSP:400-401, 507): the pole stage's images are the panorama extended to this many widths, x % cols
@@ -192,6 +206,8 @@ void frame_composite(s360_ctx* c, int pole_mask);
 void frame_render_batch(s360_ctx* c, int use_prev);
 void frame_render_slots(s360_ctx* c, const int* slots, int n, int use_prev);  // ... a subset of them (ascending, distinct)
 void set_frame_slots(s360_ctx* c, int n);
+// s360_set_debug_images: c->debug_images = on, with what it implies for the context (no pipelining, one slot; streams idle afterwards)
+void set_debug_images(s360_ctx* c, bool on);
 // The context's frame JPEG encoder (s360_set_jpeg_encode), created on first use and grown to `mcus` MCUs of 16 x 16 pixels; its
 // tables are those of the context's quality when this returns. Waits for the device when it has to build or rebuild anything.
 JpegEncoder& frame_jpeg_encoder(s360_ctx* c, long long mcus, hipStream_t st);
