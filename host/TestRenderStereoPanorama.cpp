@@ -331,10 +331,10 @@ void write_output(OutMode m, const std::string& path, const uint8_t* data, size_
 struct FrameInputs {
   std::string frame;
   std::vector<pngio::Image> side;
-  pngio::Image top, bottom, bottom2, mask1, mask2;
+  pngio::Image top, bottom, bottom2;  // (bottom2: --enable_pole_removal's secondary bottom camera; the masks are the run's, below)
   // --device_input_png: the file of a camera whose image the device decodes (its pngio::Image then holds the size only); else empty
   std::vector<std::vector<uint8_t>> sideFile;
-  std::vector<uint8_t> topFile, bottomFile;
+  std::vector<uint8_t> topFile, bottomFile, bottom2File;
   long binFrame = -1;  // --bin_list: the frame's index in the containers (nothing is decoded on the host)
 };
 // --bin_list: where a rig camera's frames are, and the ISP that develops them
@@ -382,6 +382,33 @@ void assign_pole_units(Job& J) {
     J.need[r] |= 1 << (u & 1);  // poleToSideFlowThread reads the whole side panorama of its eye
   }
   J.need[0] = 3;  // the root composites both eyes
+}
+
+// --enable_pole_removal: the two red masks are properties of the rig, not of a frame (PoleRemoval.cpp:48-66 reads them with every
+// frame). They are read ONCE per run, whatever the mode, and handed to every context that renders pole removal
+// (s360_set_pole_masks: the library computes pole removal's alpha planes once); a frame brings only the secondary camera's image.
+struct PoleMasks { pngio::Image m1, m2; };
+pngio::Image load_png(const std::string& path, bool keep_alpha);
+std::string pole_mask_message(const Job& J) {
+  return "missing or bad pole mask:" + J.F.s("bottom_pole_masks_dir") + "/" + J.cams[J.bi].id + ".png," + J.F.s("bottom_pole_masks_dir") + "/" + J.cams[J.b2].id + ".png";
+}
+const PoleMasks& pole_masks(const Job& J) {
+  static std::once_flag once;
+  static PoleMasks pm;
+  std::call_once(once, [&] {
+    const std::string masks = J.F.s("bottom_pole_masks_dir");
+    std::thread second([&] { pm.m2 = load_png(masks + "/" + J.cams[J.b2].id + ".png", false); });
+    pm.m1 = load_png(masks + "/" + J.cams[J.bi].id + ".png", false);
+    second.join();
+  });
+  return pm;
+}
+void hand_pole_masks(const Job& J) {
+  if (!J.prm.enable_pole_removal) return;
+  const PoleMasks& pm = pole_masks(J);
+  if (pm.m1.w <= 0 || pm.m1.h <= 0 || pm.m2.w != pm.m1.w || pm.m2.h != pm.m1.h) die(pole_mask_message(J));
+  for (size_t r = 0; r < J.ctx.size(); ++r)
+    if (J.unitMask[r] & 12) ck(s360_set_pole_masks(J.ctx[r], pm.m1.px.data(), pm.m2.px.data(), pm.m1.w, pm.m1.h), J.ctx[r]);
 }
 
 // --device_input_png / --device_input_jpeg: how many camera files took which path (--v 1)
@@ -453,18 +480,14 @@ FrameInputs load_frame(const Job& J, const std::string& frame, FrameInputs recyc
   if (J.prm.enable_top) th.emplace_back([&] { load_camera_image(dev, devJ, imgs + "/" + J.cams[J.ti].id + "/" + frame + ".png", in.top, in.topFile); });  // TRSP:652
   if (J.prm.enable_bottom) {
     th.emplace_back([&] { load_camera_image(dev, devJ, imgs + "/" + J.cams[J.bi].id + "/" + frame + ".png", in.bottom, in.bottomFile); });  // TRSP:602
-    if (J.prm.enable_pole_removal) {  // PoleRemoval.cpp:48-66
-      const std::string masks = J.F.s("bottom_pole_masks_dir");
-      th.emplace_back([&] { in.bottom2 = load_png(imgs + "/" + J.cams[J.b2].id + "/" + frame + ".png", false); });
-      th.emplace_back([&, masks] { in.mask1 = load_png(masks + "/" + J.cams[J.bi].id + ".png", false); });
-      th.emplace_back([&, masks] { in.mask2 = load_png(masks + "/" + J.cams[J.b2].id + ".png", false); });
-    }
+    if (J.prm.enable_pole_removal)  // PoleRemoval.cpp:48-66 (the secondary camera's image; a camera file like the others)
+      th.emplace_back([&] { load_camera_image(dev, devJ, imgs + "/" + J.cams[J.b2].id + "/" + frame + ".png", in.bottom2, in.bottom2File); });
   }
   for (auto& t : th) t.join();
   if (J.prm.enable_pole_removal) {
     const pngio::Image& im = in.bottom;
-    if (in.bottom2.w != im.w || in.bottom2.h != im.h || in.mask1.w != im.w || in.mask1.h != im.h || in.mask2.w != im.w || in.mask2.h != im.h)
-      die("missing or bad pole mask:" + J.F.s("bottom_pole_masks_dir") + "/" + J.cams[J.bi].id + ".png," + J.F.s("bottom_pole_masks_dir") + "/" + J.cams[J.b2].id + ".png");
+    const PoleMasks& pm = pole_masks(J);
+    if (in.bottom2.w != im.w || in.bottom2.h != im.h || pm.m1.w != im.w || pm.m1.h != im.h || pm.m2.w != im.w || pm.m2.h != im.h) die(pole_mask_message(J));
   }
   return in;
 }
@@ -487,6 +510,7 @@ void upload_frame(const Job& J, const FrameInputs& in) {
     for (int k = 0; k < J.P; ++k) send(J.cams[J.sideIdx[k]].id, k);
     if (J.prm.enable_top) send(J.cams[J.ti].id, S360_CAMERA_TOP);
     if (J.prm.enable_bottom) send(J.cams[J.bi].id, S360_CAMERA_BOTTOM);
+    if (J.prm.enable_pole_removal) send(J.cams[J.b2].id, S360_CAMERA_BOTTOM2);
     return;
   }
   for (int r = 0; r < G; ++r) {
@@ -508,6 +532,7 @@ void upload_frame(const Job& J, const FrameInputs& in) {
         ck(s360_frame_upload_side(J.ctx[r], k, in.side[k].px.data(), in.side[k].w, in.side[k].h, in.side[k].c), J.ctx[r]);
     if (J.unitMask[r] & 3) by_file(S360_CAMERA_TOP, in.topFile);
     if (J.unitMask[r] & 12) by_file(S360_CAMERA_BOTTOM, in.bottomFile);
+    if ((J.unitMask[r] & 12) && J.prm.enable_pole_removal) by_file(S360_CAMERA_BOTTOM2, in.bottom2File);
     if (!cams.empty()) ck(s360_frame_upload_png(J.ctx[r], (int)cams.size(), cams.data(), files.data(), bytes.data()), J.ctx[r]);
     if (!camsJ.empty()) ck(s360_frame_upload_jpeg(J.ctx[r], (int)camsJ.size(), camsJ.data(), filesJ.data(), bytesJ.data()), J.ctx[r]);
   }
@@ -516,8 +541,7 @@ void upload_frame(const Job& J, const FrameInputs& in) {
     if ((J.unitMask[r] & 3) && in.topFile.empty()) ck(s360_frame_upload_top(c, in.top.px.data(), in.top.w, in.top.h), c);
     if (J.unitMask[r] & 12) {
       if (in.bottomFile.empty()) ck(s360_frame_upload_bottom(c, in.bottom.px.data(), in.bottom.w, in.bottom.h), c);
-      if (J.prm.enable_pole_removal)
-        ck(s360_frame_upload_pole_removal(c, in.bottom2.px.data(), in.mask1.px.data(), in.mask2.px.data(), in.bottom.w, in.bottom.h), c);
+      if (J.prm.enable_pole_removal && in.bottom2File.empty()) ck(s360_frame_upload_bottom2(c, in.bottom2.px.data(), in.bottom2.w, in.bottom2.h), c);
     }
   }
 }
@@ -1116,7 +1140,6 @@ std::string frame_path(const std::string& pattern, const std::string& frame) {
 static void open_bins(Job& J) {
   const Flags& F = J.F;
   if (J.ctx.size() != 1) die("--bin_list feeds one GPU (an ISP object feeds one context): not with --num_gpus");
-  if (J.prm.enable_pole_removal) die("--bin_list is not available with --enable_pole_removal");
   std::istringstream list(F.s("bin_list"));
   std::string path;
   std::map<uint32_t, std::pair<const footage::Footage*, size_t>> bySerial;
@@ -1167,6 +1190,7 @@ static void open_bins(Job& J) {
   for (int k = 0; k < J.P; ++k) want(J.sideIdx[k]);
   if (J.prm.enable_top) want(J.ti);
   if (J.prm.enable_bottom) want(J.bi);
+  if (J.prm.enable_pole_removal) want(J.b2);  // the secondary bottom camera: its container and ISP configuration too
 }
 
 // Flags -> rig, parameters, required arguments (TRSP:717-721): common to a job and to a batch of streams
@@ -1239,6 +1263,7 @@ static int run_job(const Flags& flags) {
   J.bounds.assign(1, 0);
   for (int r = 0; r < G; ++r) J.bounds.push_back(J.bounds.back() + J.P / G + (r < J.P % G ? 1 : 0));  // 14 over 8 -> 2,2,2,2,2,2,1,1
   assign_pole_units(J);
+  hand_pole_masks(J);
   if (G > 1) {
     if (s360_comm_init_all(J.ctx.data(), G) < 0) die(s360_last_error(nullptr));
     for (int r = 0; r < G; ++r) ck(s360_frame_set_partition(J.ctx[r], J.bounds[r], J.bounds[r + 1]), J.ctx[r]);
@@ -1460,6 +1485,7 @@ static int run_stream_batch(const Flags& flags, const std::vector<Segment>& segs
   J.extW = int(float(J.prm.eqr_width) * 1.2f);
   J.bounds = {0, J.P};
   assign_pole_units(J);
+  hand_pole_masks(J);
   ck(s360_set_frame_slots(ctx, S), ctx);
   ck(s360_set_output_double_buffer(ctx, 1), ctx);  // step k is fetched while step k+1 renders
   if (!F.s("bin_list").empty()) {  // every stream's frames straight from the capture's containers: no PNG is inflated

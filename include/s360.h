@@ -67,7 +67,8 @@ typedef struct s360_params {
   char side_flow_alg[32];  /* "pixflow_low" | "pixflow_search_20" */
   char polar_flow_alg[32];
   int32_t enable_pole_removal;    /* TRSP:58: merge the two bottom cameras to erase the tripod pole (needs the secondary
-                                     bottom image and the red pole masks: s360_frame_upload_pole_removal) */
+                                     bottom image and the red pole masks: s360_frame_upload_pole_removal, or
+                                     s360_set_pole_masks + S360_CAMERA_BOTTOM2 / s360_frame_upload_bottom2, s360_pole_inputs.h) */
   char poleremoval_flow_alg[32];  /* "" = "pixflow_low" */
 } s360_params;
 
@@ -507,8 +508,9 @@ typedef struct s360_camera_isp_gen_args {
 int s360_isp_pipe_generated(s360_isp* isp, const s360_camera_isp_gen_args* args);
 /* A camera's raw Bayer frame through the ISP straight into a frame's source slot, on the context's upload stream and
  * without leaving the device — the reference's chain through files (Unpacker writes the ISP's 16-bit result as a PNG,
- * RigDescription::loadSideCameraImages / imread decodes it to 8 bits = its high byte). camera: side index, or
- * S360_CAMERA_TOP / S360_CAMERA_BOTTOM. The ISP object must have output_bpp 16 and live on the context's device; it may
+ * RigDescription::loadSideCameraImages / imread decodes it to 8 bits = its high byte). camera: side index,
+ * S360_CAMERA_TOP / S360_CAMERA_BOTTOM, or — on a context with enable_pole_removal — S360_CAMERA_BOTTOM2, the secondary bottom
+ * camera (s360_pole_inputs.h). The ISP object must have output_bpp 16 and live on the context's device; it may
  * be shared by all cameras of a rig that use one configuration (cameras of different resolutions included), but it
  * feeds ONE context: its kernels run on that context's upload stream over the object's own buffers, so a second context
  * using it is refused with S360_ERR_STATE — create one ISP object per context. Replaces s360_frame_upload_side / _top /
@@ -537,5 +539,6 @@ int s360_isp_config_tables(const s360_isp_config* cfg, float* ccm9, float* lut, 
 #include "s360_input_png.h" /* ... and those camera files decoded on the device into a frame's source slots */
 #include "s360_input_jpeg.h" /* ... and camera files that are baseline JPEGs, decoded on the device the same way */
 #include "s360_frame_jpeg.h" /* the finished frame as a JPEG file, encoded on the device: a .jpg output path */
+#include "s360_pole_inputs.h" /* pole removal: the secondary bottom camera on every input path, the masks resident per context */
 #include "s360_debug_images.h" /* the reference's --save_debug_images files of a frame; pole removal as an operator */
 #endif /* S360_H_ */

@@ -36,7 +36,7 @@ int s360_decode_input_jpeg_batch(s360_ctx* ctx, int n, const uint8_t* const* fil
                                  const size_t* cap_bytes, int* info_out);
 
 /* n camera images of the selected slot's frame from their files — the contract of s360_frame_upload_png: cameras[i] is a side
- * index, S360_CAMERA_TOP or S360_CAMERA_BOTTOM (every camera at most once), files[i] / bytes[i] its file, which must be decodable.
+ * index, S360_CAMERA_TOP, S360_CAMERA_BOTTOM or (enable_pole_removal) S360_CAMERA_BOTTOM2 (every camera at most once), files[i] / bytes[i] its file, which must be decodable.
  * The side images of a call must all have the same size, and the size of the side images handed in before (the rule of
  * s360_frame_upload_side). The files' scans are copied and decoded on the context's upload stream; the last kernel writes the
  * source slots directly — a side slot with the alpha ramp s360_frame_upload_side gives a 3-channel image, a pole slot with alpha
@@ -44,8 +44,8 @@ int s360_decode_input_jpeg_batch(s360_ctx* ctx, int n, const uint8_t* const* fil
  * SYNCHRONOUS, unlike the pixel uploads: the call holds the context until every file's status is known, so files[] may be reused as
  * soon as it returns. On success the images count as uploaded exactly as after s360_frame_upload_side / _top / _bottom. On failure
  * (S360_ERR_INVALID_ARG, "image <i>" in the message, s360_jpeg_decode_failure says which and why) NOTHING is marked as uploaded, and
- * what the slots of this call's cameras hold is unspecified until they are uploaded again. Pole removal's secondary image and masks
- * stay on s360_frame_upload_pole_removal. */
+ * what the slots of this call's cameras hold is unspecified until they are uploaded again. Pole removal's masks come through
+ * s360_set_pole_masks or s360_frame_upload_pole_removal. */
 int s360_frame_upload_jpeg(s360_ctx* ctx, int n, const int* cameras, const uint8_t* const* files, const size_t* bytes);
 
 /* The last decode call on this context (either entry point above): counts = {files, subsequences (of 4096 scan bits), synchronisation

@@ -37,8 +37,8 @@ int s360_input_png_decodable(const uint8_t* file, size_t n, int info[5]);
 int s360_decode_input_png_batch(s360_ctx* ctx, int n, const uint8_t* const* files, const size_t* bytes, void* const* out,
                                 const size_t* cap_bytes, int keep16, int* info_out);
 
-/* n camera images of the selected slot's frame from their files: cameras[i] is a side index, S360_CAMERA_TOP or
- * S360_CAMERA_BOTTOM (every camera at most once), files[i] / bytes[i] its file. Every file must be decodable with colour type 2,
+/* n camera images of the selected slot's frame from their files: cameras[i] is a side index, S360_CAMERA_TOP,
+ * S360_CAMERA_BOTTOM or, on a context with enable_pole_removal, S360_CAMERA_BOTTOM2 (s360_pole_inputs.h; every camera at most once), files[i] / bytes[i] its file. Every file must be decodable with colour type 2,
  * depth 8 or 16 (a 16-bit file gives its high bytes, as s360_frame_upload_raw does). The side images of a call must all have the
  * same size, and the size of the side images handed in before (the rule of s360_frame_upload_side). The files' bytes are copied
  * and decoded on the context's upload stream by one inflate launch and one unfilter launch that writes the source slots directly —
@@ -48,7 +48,7 @@ int s360_decode_input_png_batch(s360_ctx* ctx, int n, const uint8_t* const* file
  * known (the locking of s360_frame_set_prev_images_png), so files[] may be reused as soon as it returns. On success the images
  * count as uploaded exactly as after s360_frame_upload_side / _top / _bottom. On failure (S360_ERR_INVALID_ARG, "image <i>" in
  * the message, s360_png_decode_failure says which and why) NOTHING is marked as uploaded, and what the slots of this call's
- * cameras hold is unspecified until they are uploaded again. Pole removal's secondary image and masks stay on
+ * cameras hold is unspecified until they are uploaded again. Pole removal's masks come through s360_set_pole_masks or
  * s360_frame_upload_pole_removal. */
 int s360_frame_upload_png(s360_ctx* ctx, int n, const int* cameras, const uint8_t* const* files, const size_t* bytes);
 

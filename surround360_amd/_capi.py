@@ -109,6 +109,9 @@ INPUT_PNG_SYMBOLS = ("s360_input_png_decodable", "s360_decode_input_png_batch", 
 # ... and every symbol include/s360_input_jpeg.h declares (camera images as baseline JPEG files decoded on the device)
 INPUT_JPEG_SYMBOLS = ("s360_input_jpeg_decodable", "s360_decode_input_jpeg_batch", "s360_frame_upload_jpeg", "s360_jpeg_decode_stats",
                       "s360_jpeg_decode_failure")
+# ... and every symbol include/s360_pole_inputs.h declares (pole removal's secondary camera as a camera; the masks resident per context)
+POLE_INPUTS_SYMBOLS = ("s360_frame_upload_bottom2", "s360_set_pole_masks")
+S360_CAMERA_BOTTOM2 = -3
 # ... and its test tap, include/s360_debug_input_jpeg.h
 DEBUG_INPUT_JPEG_SYMBOLS = ("s360_debug_input_jpeg_blocks",)
 # ... and every symbol include/s360_frame_jpeg.h declares (a finished frame's equirect and cubemap as JPEG files encoded on the device)
@@ -257,6 +260,10 @@ def lib():
         L.s360_jpeg_decode_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_int]
         L.s360_jpeg_decode_failure.restype = C.c_int
         L.s360_jpeg_decode_failure.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.s360_frame_upload_bottom2.restype = C.c_int
+        L.s360_frame_upload_bottom2.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.s360_set_pole_masks.restype = C.c_int
+        L.s360_set_pole_masks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.s360_debug_input_jpeg_blocks.restype = C.c_int
         L.s360_debug_input_jpeg_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.s360_set_jpeg_encode.restype = C.c_int

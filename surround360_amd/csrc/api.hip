@@ -423,6 +423,16 @@ int s360_frame_upload_pole_removal(s360_ctx* c, const uint8_t* bottom2, const ui
     frame_upload_pole_removal(c, bottom2, mask, mask2, w, h);
   });
 }
+/* ---- include/s360_pole_inputs.h ---- */
+int s360_frame_upload_bottom2(s360_ctx* c, const uint8_t* bgr, int w, int h) {
+  return frame_guard(c, [&] { need(c && bgr && w > 0 && h > 0, "bad argument"); frame_upload_bottom2(c, bgr, w, h); });
+}
+int s360_set_pole_masks(s360_ctx* c, const uint8_t* mask, const uint8_t* mask2, int w, int h) {
+  return frame_guard(c, [&] {
+    need(c && ((mask && mask2 && w > 0 && h > 0) || (!mask && !mask2 && w == 0 && h == 0)), "bad argument");
+    set_pole_masks(c, mask, mask2, w, h);
+  });
+}
 int s360_frame_set_prev_pole_removal(s360_ctx* c, const float* flow, const uint8_t* bottom_image, const uint8_t* bottom_image2,
                                      int w, int h) {
   return frame_guard(c, [&] {

@@ -574,7 +574,7 @@ int s360_frame_upload_png(s360_ctx* c, int n, const int* cameras, const uint8_t*
     FrameState& F = frame_state(c);
     need(F.P <= 64, "more than 64 side cameras");
     for (int i = 0; i < n; ++i) {
-      need(cameras[i] >= S360_CAMERA_BOTTOM && cameras[i] < F.P, "camera index out of range");
+      need(upload_camera_valid(c, cameras[i], F.P), "camera index out of range");
       for (int j = 0; j < i; ++j) need(cameras[j] != cameras[i], "a camera is named twice");
     }
     const std::vector<PngBandedInfo> info = png_parse_all(c, n, files, bytes, true);

@@ -135,6 +135,12 @@ struct s360_ctx {
   struct CubeMaps { int fw = 0, fh = 0, W = 0, H = 0, lds_pixels = 0; s360::DevBuf maps, packed[2], tiles[2]; };
   std::vector<std::unique_ptr<CubeMaps>> cubeMaps;
   bool maps_ready = false;
+  // s360_set_pole_masks (include/s360_pole_inputs.h): pole removal's three alpha planes of poleMaskW x poleMaskH bytes, constants of
+  // the masks, the rig and std_alpha_feather_size, shared by all slots — [0] the bottom camera's flow input, [1] the secondary camera's
+  // (already turned by 180 degrees when the rig says so), [2] the merged image
+  s360::DevBuf poleAlpha[3];
+  int poleMaskW = 0, poleMaskH = 0;
+  bool havePoleMasks = false;
   hipEvent_t evMaps = nullptr;  // behind the kernels that built the float maps (the pack kernels may run on another stream)
   void make_current() const { S360_HIP(hipSetDevice(device)); }
 };

@@ -315,8 +315,22 @@ void frame_upload_side(s360_ctx* c, int idx, const uint8_t* img, int w, int h, i
   F.have_side = true;
   F.side_uploaded |= 1ull << idx;
 }
+bool upload_camera_valid(const s360_ctx* c, int camera, int P) {
+  return camera < P && camera >= (c->P.enable_pole_removal ? S360_CAMERA_BOTTOM2 : S360_CAMERA_BOTTOM);
+}
+void check_bottom_sizes(s360_ctx* c, int bw, int bh, int b2w, int b2h) {
+  if (!c->P.enable_pole_removal) return;
+  FrameState& F = frame_state(c);
+  if (c->havePoleMasks && ((bw && (bw != c->poleMaskW || bh != c->poleMaskH)) || (b2w && (b2w != c->poleMaskW || b2h != c->poleMaskH))))
+    throw Error(S360_ERR_INVALID_ARG, "the bottom images must have the size of the context's pole masks (s360_set_pole_masks)");
+  if (!bw && F.have_bottom) { bw = F.poleW; bh = F.poleH; }
+  if (!b2w && F.have_bottom2) { b2w = F.bot2W; b2h = F.bot2H; }
+  if (bw && b2w && (bw != b2w || bh != b2h))
+    throw Error(S360_ERR_INVALID_ARG, "the secondary bottom image and the pole masks must have the bottom camera's size");
+}
 void frame_upload_pole(s360_ctx* c, bool top, const uint8_t* bgr, int w, int h) {
   FrameState& F = frame_state(c);
+  if (!top) check_bottom_sizes(c, w, h, 0, 0);
   ensure_upload_stream(c);
   if (top) { F.topW = w; F.topH = h; } else { F.poleW = w; F.poleH = h; }
   const size_t n = (size_t)w * h;
@@ -330,20 +344,38 @@ void frame_upload_pole(s360_ctx* c, bool top, const uint8_t* bgr, int w, int h) 
   (top ? F.have_top : F.have_bottom) = true;
 }
 
+void frame_upload_bottom2(s360_ctx* c, const uint8_t* bgr, int w, int h) {
+  if (!c->P.enable_pole_removal) throw Error(S360_ERR_STATE, "this context does not run pole removal");
+  FrameState& F = frame_state(c);
+  check_bottom_sizes(c, 0, 0, w, h);
+  ensure_upload_stream(c);
+  const size_t n = (size_t)w * h;
+  F.botSrc2.ensure(n * sizeof(uchar4));
+  F.staging.ensure(n * 4);
+  upload_bytes(c, F.staging.p, bgr, n * 3);
+  if (c->havePoleSrcFree) S360_HIP(hipStreamWaitEvent(c->stUp, c->evPoleSrcFree, 0));
+  launch_bgr_to_bgra(c->stUp, F.staging.as<uint8_t>(), 3, F.botSrc2.as<uchar4>(), n);
+  uploads_done(c);
+  F.bot2W = w; F.bot2H = h;
+  F.have_bottom2 = true;
+}
+
 // A camera's raw Bayer frame through the ISP straight into the frame's source slot ("feeding the GPU
 // directly"): what the reference does through files — Unpacker writes the ISP's 16-bit result as a PNG, the renderer's
 // imread decodes it to 8 bits, i.e. keeps the high byte — happens on the upload stream without leaving the device.
-// which: side index, -1 top, -2 bottom.
+// which: side index, -1 top, -2 bottom, -3 (pole removal) the secondary bottom camera.
 // bits: 16 = raw16 samples; 8 / 12 = the sensor's packed bytes as a capture container holds them (widened on the device).
 void frame_upload_raw(s360_ctx* c, s360_isp* isp, int which, const void* raw, int bits, int inW, int inH) {
   if (isp->cfg.output_bpp != 16)
     throw Error(S360_ERR_INVALID_ARG, "uploading through the ISP needs output_bpp 16 (the reference's chain stores 16-bit PNGs and imread keeps their high byte)");
   if (isp->device != c->device) throw Error(S360_ERR_INVALID_ARG, "the ISP object lives on another device");
   FrameState& F = frame_state(c);
-  if (which < -2 || which >= F.P) throw Error(S360_ERR_INVALID_ARG, "camera index out of range");
-  ensure_upload_stream(c);
+  if (!upload_camera_valid(c, which, F.P)) throw Error(S360_ERR_INVALID_ARG, "camera index out of range");
   const int w = inW / isp->cfg.resize, h = inH / isp->cfg.resize;
   const size_t n = (size_t)w * h;
+  if (which == S360_CAMERA_BOTTOM) check_bottom_sizes(c, w, h, 0, 0);
+  if (which == S360_CAMERA_BOTTOM2) check_bottom_sizes(c, 0, 0, w, h);
+  ensure_upload_stream(c);
   if (bits == 16) {
     upload_bytes(c, isp_raw_buffer(isp, inW, inH), raw, (size_t)inW * inH * sizeof(uint16_t));
   } else {
@@ -365,13 +397,13 @@ void frame_upload_raw(s360_ctx* c, s360_isp* isp, int which, const void* raw, in
     F.have_side = true;
     F.side_uploaded |= 1ull << which;
   } else {  // as frame_upload_pole
-    const bool top = which == -1;
-    if (top) { F.topW = w; F.topH = h; } else { F.poleW = w; F.poleH = h; }
-    DevBuf& dst = top ? F.topSrc : F.botSrc;
+    const bool top = which == S360_CAMERA_TOP, second = which == S360_CAMERA_BOTTOM2;
+    if (top) { F.topW = w; F.topH = h; } else if (second) { F.bot2W = w; F.bot2H = h; } else { F.poleW = w; F.poleH = h; }
+    DevBuf& dst = top ? F.topSrc : second ? F.botSrc2 : F.botSrc;
     dst.ensure(n * sizeof(uchar4));
     if (c->havePoleSrcFree) S360_HIP(hipStreamWaitEvent(c->stUp, c->evPoleSrcFree, 0));
     launch_bgr_to_bgra(c->stUp, F.staging.as<uint8_t>(), 3, dst.as<uchar4>(), n);
-    (top ? F.have_top : F.have_bottom) = true;
+    (top ? F.have_top : second ? F.have_bottom2 : F.have_bottom) = true;
   }
   uploads_done(c);
 }
@@ -390,6 +422,14 @@ void frame_upload_png(s360_ctx* c, const std::vector<int>& cams, const std::vect
     if (!side) F.sideSrc.ensure((size_t)F.P * info[i].w * info[i].h * sizeof(uchar4));
     side = true;
   }
+  {
+    int bw = 0, bh = 0, b2w = 0, b2h = 0;
+    for (size_t i = 0; i < cams.size(); ++i) {
+      if (cams[i] == S360_CAMERA_BOTTOM) { bw = info[i].w; bh = info[i].h; }
+      if (cams[i] == S360_CAMERA_BOTTOM2) { b2w = info[i].w; b2h = info[i].h; }
+    }
+    if (bw || b2w) check_bottom_sizes(c, bw, bh, b2w, b2h);
+  }
   std::vector<PngDecodeDst> dst(cams.size());
   for (size_t i = 0; i < cams.size(); ++i) {
     const size_t n = (size_t)info[i].w * info[i].h;
@@ -398,7 +438,7 @@ void frame_upload_png(s360_ctx* c, const std::vector<int>& cams, const std::vect
       dst[i].store = kPngStoreSide;
       dst[i].feather = c->P.side_alpha_feather_size;
     } else {
-      DevBuf& d = cams[i] == S360_CAMERA_TOP ? F.topSrc : F.botSrc;
+      DevBuf& d = cams[i] == S360_CAMERA_TOP ? F.topSrc : cams[i] == S360_CAMERA_BOTTOM2 ? F.botSrc2 : F.botSrc;
       d.ensure(n * sizeof(uchar4));
       dst[i].p = d.as<uint8_t>();
       dst[i].store = kPngStorePole;
@@ -416,6 +456,9 @@ void frame_upload_png(s360_ctx* c, const std::vector<int>& cams, const std::vect
     } else if (cams[i] == S360_CAMERA_TOP) {
       F.topW = info[i].w; F.topH = info[i].h;
       F.have_top = true;
+    } else if (cams[i] == S360_CAMERA_BOTTOM2) {
+      F.bot2W = info[i].w; F.bot2H = info[i].h;
+      F.have_bottom2 = true;
     } else {
       F.poleW = info[i].w; F.poleH = info[i].h;
       F.have_bottom = true;
@@ -436,6 +479,14 @@ void frame_upload_jpeg(s360_ctx* c, const std::vector<int>& cams, const std::vec
     if (!side) F.sideSrc.ensure((size_t)F.P * info[i].w * info[i].h * sizeof(uchar4));
     side = true;
   }
+  {
+    int bw = 0, bh = 0, b2w = 0, b2h = 0;
+    for (size_t i = 0; i < cams.size(); ++i) {
+      if (cams[i] == S360_CAMERA_BOTTOM) { bw = info[i].w; bh = info[i].h; }
+      if (cams[i] == S360_CAMERA_BOTTOM2) { b2w = info[i].w; b2h = info[i].h; }
+    }
+    if (bw || b2w) check_bottom_sizes(c, bw, bh, b2w, b2h);
+  }
   std::vector<JpegDecodeDst> dst(cams.size());
   for (size_t i = 0; i < cams.size(); ++i) {
     const size_t n = (size_t)info[i].w * info[i].h;
@@ -444,7 +495,7 @@ void frame_upload_jpeg(s360_ctx* c, const std::vector<int>& cams, const std::vec
       dst[i].store = kJpegStoreSide;
       dst[i].feather = c->P.side_alpha_feather_size;
     } else {
-      DevBuf& d = cams[i] == S360_CAMERA_TOP ? F.topSrc : F.botSrc;
+      DevBuf& d = cams[i] == S360_CAMERA_TOP ? F.topSrc : cams[i] == S360_CAMERA_BOTTOM2 ? F.botSrc2 : F.botSrc;
       d.ensure(n * sizeof(uchar4));
       dst[i].p = d.as<uint8_t>();
       dst[i].store = kJpegStorePole;
@@ -462,6 +513,9 @@ void frame_upload_jpeg(s360_ctx* c, const std::vector<int>& cams, const std::vec
     } else if (cams[i] == S360_CAMERA_TOP) {
       F.topW = info[i].w; F.topH = info[i].h;
       F.have_top = true;
+    } else if (cams[i] == S360_CAMERA_BOTTOM2) {
+      F.bot2W = info[i].w; F.bot2H = info[i].h;
+      F.have_bottom2 = true;
     } else {
       F.poleW = info[i].w; F.poleH = info[i].h;
       F.have_bottom = true;
@@ -472,6 +526,8 @@ void frame_upload_jpeg(s360_ctx* c, const std::vector<int>& cams, const std::vec
 
 void frame_upload_pole_removal(s360_ctx* c, const uint8_t* bottom2, const uint8_t* mask, const uint8_t* mask2, int w, int h) {
   FrameState& F = frame_state(c);
+  if (c->havePoleMasks)
+    throw Error(S360_ERR_STATE, "the context holds pole masks (s360_set_pole_masks): the secondary image goes through s360_frame_upload_bottom2 or S360_CAMERA_BOTTOM2");
   if (F.have_bottom && (w != F.poleW || h != F.poleH))
     throw Error(S360_ERR_INVALID_ARG, "the secondary bottom image and the pole masks must have the bottom camera's size");
   ensure_upload_stream(c);
@@ -491,34 +547,90 @@ void frame_upload_pole_removal(s360_ctx* c, const uint8_t* bottom2, const uint8_
   F.have_pr_inputs = true;
 }
 
-// featherAlphaChannel (CvUtil.cpp:140-157) of a whole BGRA image, in place.
-static void dev_feather_in_place(s360_ctx* c, uchar4* img, int w, int h) {
+// featherAlphaChannel (CvUtil.cpp:140-157) of a whole BGRA image: the feathered alpha plane, w x h bytes in the selected slot's
+// scratch (valid until the next call); the image is only read.
+static const uint8_t* dev_feathered_alpha(s360_ctx* c, const uchar4* img, int w, int h) {
   FrameState& F = frame_state(c);
   const size_t n = (size_t)w * h;
   F.a8a.ensure(n);
   F.a8b.ensure(n);
   launch_erode_alpha(c->st, img, F.a8b.as<uint8_t>(), w, h, c->P.std_alpha_feather_size);
-  const uint8_t* alpha = F.a8b.as<uint8_t>();
-  if (F.tab.gauss_ksize > 1) {
-    launch_gauss_u8(c->st, F.a8b.as<uint8_t>(), F.a8a.as<uint8_t>(), w, h, F.tab.gik.as<int>(), F.tab.gauss_ksize / 2);
-    alpha = F.a8a.as<uint8_t>();
-  }
+  if (F.tab.gauss_ksize <= 1) return F.a8b.as<uint8_t>();
+  launch_gauss_u8(c->st, F.a8b.as<uint8_t>(), F.a8a.as<uint8_t>(), w, h, F.tab.gik.as<int>(), F.tab.gauss_ksize / 2);
+  return F.a8a.as<uint8_t>();
+}
+// ... and written back into the image's alpha channel.
+static void dev_feather_in_place(s360_ctx* c, uchar4* img, int w, int h) {
+  const uint8_t* alpha = dev_feathered_alpha(c, img, w, h);
   launch_extend_wrap(c->st, img, alpha, w, h, img, w);  // extW == cols: every thread rewrites its own pixel
+}
+
+// what pole removal takes from the rig: the usable radii of the two bottom cameras, and whether the secondary image is turned
+struct PoleRemovalRig {
+  float radius, radius2;
+  bool flip180;
+  explicit PoleRemovalRig(const s360_ctx* c) {
+    const s360_camera& cam = c->rig.all[c->bottom_idx];
+    const s360_camera& cam2 = c->rig.all[c->rig.find_largest_axis_dist()];
+    radius = approximate_usable_pixels_radius(&cam);
+    radius2 = approximate_usable_pixels_radius(&cam2);
+    const double* up1 = cam.rotation + 3;
+    const double* up2 = cam2.rotation + 3;
+    flip180 = up1[0] * up2[0] + up1[1] * up2[1] + up1[2] * up2[2] < 0;  // TRSP:580
+  }
+};
+
+// s360_set_pole_masks: the three alpha planes dev_pole_removal would compute for every frame, once. Each is circleAlphaCut [+ the
+// red mask cut out] and featherAlphaChannel of an image whose colours nobody reads: the same kernels as the per-frame path, on
+// operator scratch. Not hot; the context's streams are idle before and after.
+void set_pole_masks(s360_ctx* c, const uint8_t* mask, const uint8_t* mask2, int w, int h) {
+  if (!c->P.enable_pole_removal) throw Error(S360_ERR_STATE, "this context does not run pole removal");
+  S360_HIP(hipStreamSynchronize(c->st));
+  if (c->st2) S360_HIP(hipStreamSynchronize(c->st2));
+  if (c->stUp) S360_HIP(hipStreamSynchronize(c->stUp));
+  c->havePoleMasks = false;
+  c->poleMaskW = c->poleMaskH = 0;
+  if (!mask) return;
+  if (c->bottom_idx < 0) throw Error(S360_ERR_STATE, "no bottom camera in the rig");
+  const PoleRemovalRig pr(c);
+  hipStream_t st = c->st;
+  const size_t n = (size_t)w * h;
+  c->op_a.ensure(n * sizeof(uchar4));
+  c->op_b.ensure(n * 3);
+  c->op_c.ensure(n);
+  S360_HIP(hipMemsetAsync(c->op_a.p, 0, n * sizeof(uchar4), st));
+  const uint8_t* masks[3] = {mask, mask2, nullptr};
+  for (int k = 0; k < 3; ++k) {
+    c->poleAlpha[k].ensure((n + 3) & ~(size_t)3);
+    if (masks[k]) {
+      S360_HIP(hipMemcpyAsync(c->op_b.p, masks[k], n * 3, hipMemcpyHostToDevice, st));
+      launch_red_mask(st, c->op_b.as<uint8_t>(), c->op_c.as<uint8_t>(), n);
+    }
+    launch_circle_alpha(st, c->op_a.as<uchar4>(), masks[k] ? c->op_c.as<uint8_t>() : nullptr, c->op_a.as<uchar4>(), w, h,
+                        k == 1 ? pr.radius2 : pr.radius);
+    const uint8_t* alpha = dev_feathered_alpha(c, c->op_a.as<uchar4>(), w, h);  // (the selected slot's scratch and taps: the streams are idle)
+    if (k == 1 && pr.flip180) launch_reverse_u8(st, alpha, c->poleAlpha[k].as<uint8_t>(), n);
+    else S360_HIP(hipMemcpyAsync(c->poleAlpha[k].p, alpha, n, hipMemcpyDeviceToDevice, st));
+  }
+  S360_HIP(hipStreamSynchronize(st));
+  c->poleMaskW = w;
+  c->poleMaskH = h;
+  c->havePoleMasks = true;
 }
 
 // combineBottomImagesWithPoleRemoval (PoleRemoval.cpp:32-188): merged BGRA bottom image in F.prMerged.
 static void dev_pole_removal(s360_ctx* c, FrameState& F, bool use_prev) {
-  if (!F.have_pr_inputs) throw Error(S360_ERR_STATE, "enable_pole_removal: secondary bottom image / pole masks not uploaded");
+  const bool resident = c->havePoleMasks;  // include/s360_pole_inputs.h
+  if (resident ? !F.have_bottom2 : !F.have_pr_inputs)
+    throw Error(S360_ERR_STATE, "enable_pole_removal: secondary bottom image / pole masks not uploaded");
+  if (resident && (F.poleW != c->poleMaskW || F.poleH != c->poleMaskH || F.bot2W != c->poleMaskW || F.bot2H != c->poleMaskH))
+    throw Error(S360_ERR_INVALID_ARG, "the bottom images must have the size of the context's pole masks (s360_set_pole_masks)");
   hipStream_t st = c->st;
   const int w = F.poleW, h = F.poleH;
   const size_t n = (size_t)w * h;
-  const int bi = c->bottom_idx, b2 = c->rig.find_largest_axis_dist();
-  const s360_camera& cam = c->rig.all[bi];
-  const s360_camera& cam2 = c->rig.all[b2];
-  const float radius = approximate_usable_pixels_radius(&cam), radius2 = approximate_usable_pixels_radius(&cam2);
-  const double* up1 = cam.rotation + 3;
-  const double* up2 = cam2.rotation + 3;
-  const bool flip180 = up1[0] * up2[0] + up1[1] * up2[1] + up1[2] * up2[2] < 0;  // TRSP:580
+  const PoleRemovalRig pr(c);
+  const float radius = pr.radius, radius2 = pr.radius2;
+  const bool flip180 = pr.flip180;
   const bool usePrev = use_prev && F.have_prev_pr;
   // temporal double buffer: the previous state is only kept apart when this frame reads it
   const int prv = F.last_pr, cur = usePrev ? prv ^ 1 : prv;
@@ -529,7 +641,11 @@ static void dev_pole_removal(s360_ctx* c, FrameState& F, bool use_prev) {
   F.prMerged.ensure(n * sizeof(uchar4));
   uchar4* img1 = F.prImgs[cur].as<uchar4>();
   uchar4* img2 = img1 + n;
-  {
+  if (resident) {
+    ProfScope ps(c->prof, "pole_removal_prepare");
+    launch_pole_removal_inputs(st, F.botSrc.as<uchar4>(), F.botSrc2.as<uchar4>(), c->poleAlpha[0].as<uint8_t>(),
+                               c->poleAlpha[1].as<uint8_t>(), img1, img2, n, flip180);
+  } else {
     ProfScope ps(c->prof, "pole_removal_prepare");
     launch_circle_alpha(st, F.botSrc.as<uchar4>(), F.prRed[0].as<uint8_t>(), img1, w, h, radius);
     dev_feather_in_place(c, img1, w, h);
@@ -550,10 +666,14 @@ static void dev_pole_removal(s360_ctx* c, FrameState& F, bool use_prev) {
   {
     ProfScope ps(c->prof, "pole_removal_merge");
     launch_remap_by_flow(st, img2, w, h, F.prFlow[cur].as<float2>(), F.prWarp.as<uchar4>(), F.tab.dev);
-    S360_HIP(hipMemcpyAsync(F.prMerged.p, img1, n * sizeof(uchar4), hipMemcpyDeviceToDevice, st));
-    launch_pole_removal_combine(st, F.prMerged.as<uchar4>(), F.prWarp.as<uchar4>(), n);
-    launch_circle_alpha(st, F.prMerged.as<uchar4>(), nullptr, F.prMerged.as<uchar4>(), w, h, radius);
-    dev_feather_in_place(c, F.prMerged.as<uchar4>(), w, h);
+    if (resident) {
+      launch_pole_removal_merge(st, img1, F.prWarp.as<uchar4>(), c->poleAlpha[2].as<uint8_t>(), F.prMerged.as<uchar4>(), n);
+    } else {
+      S360_HIP(hipMemcpyAsync(F.prMerged.p, img1, n * sizeof(uchar4), hipMemcpyDeviceToDevice, st));
+      launch_pole_removal_combine(st, F.prMerged.as<uchar4>(), F.prWarp.as<uchar4>(), n);
+      launch_circle_alpha(st, F.prMerged.as<uchar4>(), nullptr, F.prMerged.as<uchar4>(), w, h, radius);
+      dev_feather_in_place(c, F.prMerged.as<uchar4>(), w, h);
+    }
   }
   F.have_prev_pr = true;
   F.last_pr = cur;

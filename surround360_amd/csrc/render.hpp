@@ -113,6 +113,9 @@ struct FrameState {
   // pole removal: secondary bottom source (BGRA), red-mask planes, flow inputs [cur/prev][2][n], flow [cur/prev][n]
   DevBuf botSrc2, prRed[2], prImgs[2], prFlow[2], prTmp, prWarp, prMerged;
   bool have_pr_inputs = false, have_prev_pr = false;
+  // the secondary bottom image handed in as a camera (S360_CAMERA_BOTTOM2 / s360_frame_upload_bottom2) and its size
+  bool have_bottom2 = false;
+  int bot2W = 0, bot2H = 0;
   int last_pr = 0;
   DevBuf cubeOut;  // s360_frame_cubemap's stacked BGR cubemap (the face maps are the context's: ctx.hpp CubeMaps)
   // s360_set_cubemap_output: the stacked cubemap of the frame in outBGR[i] (the finish stage renders it behind the sharpen and in
@@ -190,7 +193,15 @@ void frame_upload_side(s360_ctx* c, int idx, const uint8_t* img, int w, int h, i
 void frame_upload_pole(s360_ctx* c, bool top, const uint8_t* bgr, int w, int h);
 void frame_upload_raw(s360_ctx* c, struct s360_isp* isp, int which, const void* raw, int bits, int inW, int inH);
 void frame_upload_pole_removal(s360_ctx* c, const uint8_t* bottom2, const uint8_t* mask, const uint8_t* mask2, int w, int h);
-// cams[i]: side index, S360_CAMERA_TOP or S360_CAMERA_BOTTOM; info[i]: files[i] parsed (png_parse_banded_input), 3 channels
+// include/s360_pole_inputs.h: the secondary bottom camera's pixels; the masks as state of the context (nullptr: cleared)
+void frame_upload_bottom2(s360_ctx* c, const uint8_t* bgr, int w, int h);
+void set_pole_masks(s360_ctx* c, const uint8_t* mask, const uint8_t* mask2, int w, int h);
+// may `camera` be named in an upload call of this context? (side index, S360_CAMERA_TOP / _BOTTOM; S360_CAMERA_BOTTOM2 with pole removal)
+bool upload_camera_valid(const s360_ctx* c, int camera, int P);
+// the size rules of the two bottom sources before anything is enqueued: (bw, bh) / (b2w, b2h) = the bottom / secondary image of this
+// call, 0 = not part of it. Throws S360_ERR_INVALID_ARG.
+void check_bottom_sizes(s360_ctx* c, int bw, int bh, int b2w, int b2h);
+// cams[i]: side index, S360_CAMERA_TOP, S360_CAMERA_BOTTOM or (pole removal) S360_CAMERA_BOTTOM2; info[i]: files[i] parsed (png_parse_banded_input), 3 channels
 void frame_upload_png(s360_ctx* c, const std::vector<int>& cams, const std::vector<const uint8_t*>& files,
                       const std::vector<PngBandedInfo>& info);
 // ... and the same from baseline JPEG files (include/s360_input_jpeg.h); info[i]: files[i] parsed (jpeg_in_parse)

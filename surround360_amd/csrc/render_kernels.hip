@@ -588,22 +588,96 @@ __global__ __launch_bounds__(256) void k_circle_alpha(const uchar4* __restrict__
   if (red && red[i]) p.w = 0;
   dst[i] = p;
 }
-// the alpha-weighted merge of the primary bottom image with the warped secondary one (PoleRemoval.cpp:153-180)
+// the alpha-weighted merge of the primary bottom image with the warped secondary one (PoleRemoval.cpp:153-180): one pixel; false = p1 stays
+__device__ __forceinline__ bool pole_removal_combine_px(uchar4& p1, const uchar4 p2) {
+  const float alpha = (float)p1.w / 255.0f, alpha2 = (float)p2.w / 255.0f;
+  if (!(alpha < 1.0f && alpha2 > 0.0f)) return false;
+  const float a1 = alpha, a2 = 1.0f - alpha;
+  p1.x = (unsigned char)(a1 * (float)p1.x + a2 * (float)p2.x);
+  p1.y = (unsigned char)(a1 * (float)p1.y + a2 * (float)p2.y);
+  p1.z = (unsigned char)(a1 * (float)p1.z + a2 * (float)p2.z);
+  p1.w = 255;
+  return true;
+}
 __global__ __launch_bounds__(256) void k_pole_removal_combine(uchar4* __restrict__ bottom, const uchar4* __restrict__ warped2,
                                                               size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   uchar4 p1 = bottom[i];
-  const uchar4 p2 = warped2[i];
-  const float alpha = (float)p1.w / 255.0f, alpha2 = (float)p2.w / 255.0f;
-  if (alpha < 1.0f && alpha2 > 0.0f) {
-    const float a1 = alpha, a2 = 1.0f - alpha;
-    p1.x = (unsigned char)(a1 * (float)p1.x + a2 * (float)p2.x);
-    p1.y = (unsigned char)(a1 * (float)p1.y + a2 * (float)p2.y);
-    p1.z = (unsigned char)(a1 * (float)p1.z + a2 * (float)p2.z);
-    p1.w = 255;
-    bottom[i] = p1;
+  if (pole_removal_combine_px(p1, warped2[i])) bottom[i] = p1;
+}
+// ---- pole removal with resident alpha planes (include/s360_pole_inputs.h) ----
+// A thread owns the four pixels [4g, 4g + 4) of the n = w * h: 16-byte accesses and the four alpha bytes as one word wherever the
+// group is whole and its addresses are aligned, pixel by pixel otherwise. Every index comes from n, none from the grid.
+__device__ __forceinline__ unsigned px_with_alpha(unsigned px, unsigned a) { return (px & 0xffffffu) | (a << 24); }
+__device__ __forceinline__ uint4 px4_with_alpha(uint4 p, unsigned a) {  // pixel k's alpha in byte k of a
+  return make_uint4(px_with_alpha(p.x, a & 0xffu), px_with_alpha(p.y, (a >> 8) & 0xffu), px_with_alpha(p.z, (a >> 16) & 0xffu),
+                    px_with_alpha(p.w, a >> 24));
+}
+// Both flow inputs of a frame. img2 lies n pixels behind img1 (render.hip): its groups, and the groups of bot2 read back to front
+// (pixel i comes from n - 1 - i: the flip by 180 degrees), are 16-byte aligned only when n is a multiple of 4.
+__global__ __launch_bounds__(256) void k_pole_removal_inputs(const uchar4* __restrict__ bot, const uchar4* __restrict__ bot2,
+                                                             const uint8_t* __restrict__ a1, const uint8_t* __restrict__ a2,
+                                                             uchar4* __restrict__ img1, uchar4* __restrict__ img2, size_t n,
+                                                             int flip180) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g > (n - 1) / 4) return;  // (n >= 1: the launcher)
+  const size_t i0 = g * 4;
+  const bool whole = n - i0 >= 4;
+  if (whole)
+    reinterpret_cast<uint4*>(img1)[g] = px4_with_alpha(reinterpret_cast<const uint4*>(bot)[g], reinterpret_cast<const unsigned*>(a1)[g]);
+  if (whole && (n & 3) == 0) {
+    uint4 p;
+    if (flip180) {
+      const uint4 q = reinterpret_cast<const uint4*>(bot2)[n / 4 - 1 - g];
+      p = make_uint4(q.w, q.z, q.y, q.x);
+    } else {
+      p = reinterpret_cast<const uint4*>(bot2)[g];
+    }
+    reinterpret_cast<uint4*>(img2)[g] = px4_with_alpha(p, reinterpret_cast<const unsigned*>(a2)[g]);
+    return;
   }
+  const size_t i1 = whole ? i0 + 4 : n;
+  for (size_t i = i0; i < i1; ++i) {
+    if (!whole) {
+      uchar4 p = bot[i];
+      p.w = a1[i];
+      img1[i] = p;
+    }
+    uchar4 p = bot2[flip180 ? n - 1 - i : i];
+    p.w = a2[i];
+    img2[i] = p;
+  }
+}
+// The merged bottom image: k_pole_removal_combine's colours of (img1, warped2) under the alpha plane a3 = feather(circle).
+__global__ __launch_bounds__(256) void k_pole_removal_merge(const uchar4* __restrict__ img1, const uchar4* __restrict__ warped2,
+                                                            const uint8_t* __restrict__ a3, uchar4* __restrict__ merged, size_t n) {
+  const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g > (n - 1) / 4) return;
+  const size_t i0 = g * 4;
+  if (n - i0 >= 4) {
+    const uint4 v1 = reinterpret_cast<const uint4*>(img1)[g], v2 = reinterpret_cast<const uint4*>(warped2)[g];
+    uchar4 p[4] = {__builtin_bit_cast(uchar4, v1.x), __builtin_bit_cast(uchar4, v1.y), __builtin_bit_cast(uchar4, v1.z),
+                   __builtin_bit_cast(uchar4, v1.w)};
+    const uchar4 q[4] = {__builtin_bit_cast(uchar4, v2.x), __builtin_bit_cast(uchar4, v2.y), __builtin_bit_cast(uchar4, v2.z),
+                         __builtin_bit_cast(uchar4, v2.w)};
+    for (int k = 0; k < 4; ++k) (void)pole_removal_combine_px(p[k], q[k]);
+    reinterpret_cast<uint4*>(merged)[g] =
+        px4_with_alpha(make_uint4(__builtin_bit_cast(unsigned, p[0]), __builtin_bit_cast(unsigned, p[1]), __builtin_bit_cast(unsigned, p[2]),
+                                  __builtin_bit_cast(unsigned, p[3])),
+                       reinterpret_cast<const unsigned*>(a3)[g]);
+    return;
+  }
+  for (size_t i = i0; i < n; ++i) {
+    uchar4 p = img1[i];
+    (void)pole_removal_combine_px(p, warped2[i]);
+    p.w = a3[i];
+    merged[i] = p;
+  }
+}
+__global__ __launch_bounds__(256) void k_reverse_u8(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[n - 1 - i];
 }
 
 // two pixels per thread (camW and overlapW even: both sides of the copy are 8-byte aligned)
@@ -1947,6 +2021,18 @@ void launch_circle_alpha(hipStream_t st, const uchar4* src, const uint8_t* red, 
 }
 void launch_pole_removal_combine(hipStream_t st, uchar4* bottom, const uchar4* warped2, size_t n) {
   hipLaunchKernelGGL(k_pole_removal_combine, dim3(cdiv(n, 256)), dim3(256), 0, st, bottom, warped2, n);
+}
+void launch_pole_removal_inputs(hipStream_t st, const uchar4* bot, const uchar4* bot2, const uint8_t* a1, const uint8_t* a2,
+                                uchar4* img1, uchar4* img2, size_t n, bool flip180) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pole_removal_inputs, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, st, bot, bot2, a1, a2, img1, img2, n, flip180 ? 1 : 0);
+}
+void launch_pole_removal_merge(hipStream_t st, const uchar4* img1, const uchar4* warped2, const uint8_t* a3, uchar4* merged, size_t n) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pole_removal_merge, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, st, img1, warped2, a3, merged, n);
+}
+void launch_reverse_u8(hipStream_t st, const uint8_t* src, uint8_t* dst, size_t n) {
+  hipLaunchKernelGGL(k_reverse_u8, dim3(cdiv(n, 256)), dim3(256), 0, st, src, dst, n);
 }
 void launch_crop_overlaps(hipStream_t st, const uchar4* proj, int camW, int camH, int P, int overlapW, uchar4* out,
                           int p0, int p1) {

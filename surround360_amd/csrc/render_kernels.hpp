@@ -135,6 +135,13 @@ void launch_red_mask(hipStream_t st, const uint8_t* bgr, uint8_t* red, size_t n)
 void launch_circle_alpha(hipStream_t st, const uchar4* src, const uint8_t* red /*nullable*/, uchar4* dst, int w, int h,
                          float radius);
 void launch_pole_removal_combine(hipStream_t st, uchar4* bottom, const uchar4* warped2, size_t n);
+// ... with the alpha planes resident (include/s360_pole_inputs.h; a1, a2, a3: n bytes each, 4-byte aligned; images 16-byte aligned)
+// both flow inputs in one pass: img1 = colours of bot with alpha a1, img2 = colours of bot2 (read back to front when flip180) with a2
+void launch_pole_removal_inputs(hipStream_t st, const uchar4* bot, const uchar4* bot2, const uint8_t* a1, const uint8_t* a2,
+                                uchar4* img1, uchar4* img2, size_t n, bool flip180);
+// merged = launch_pole_removal_combine's colours of (img1, warped2) with alpha a3, in one pass
+void launch_pole_removal_merge(hipStream_t st, const uchar4* img1, const uchar4* warped2, const uint8_t* a3, uchar4* merged, size_t n);
+void launch_reverse_u8(hipStream_t st, const uint8_t* src, uint8_t* dst, size_t n);  // dst[i] = src[n - 1 - i]
 void launch_pack_bgr(hipStream_t st, const uchar4* src, int w, int h, uint8_t* dst);
 // sharpen (Filter.h:40-127) on BGRA in place, lp scratch same size
 int sharpen_max_images();  // images one launch_sharpen_many call takes

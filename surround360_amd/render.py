@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import HINT, Camera, Geometry, Params, S360Error, check, lib
+from ._capi import HINT, S360_CAMERA_BOTTOM2, Camera, Geometry, Params, S360Error, check, lib
 
 
 def _p(a):
@@ -466,7 +466,8 @@ class Context:
 
     def upload_raw(self, isp, camera, raw16):
         """A camera's raw Bayer frame (H x W uint16) through `isp` (surround360_amd.isp.CameraIsp, output_bpp 16) into
-        this frame's source slot on the device. camera: side index, -1 top, -2 bottom."""
+        this frame's source slot on the device. camera: side index, -1 top, -2 bottom, -3 (S360_CAMERA_BOTTOM2, on a context with
+        enable_pole_removal) the secondary bottom camera."""
         r = np.ascontiguousarray(raw16, np.uint16)
         self._ck(lib().s360_frame_upload_raw(self.h, isp.h, int(camera), _p(r), r.shape[1], r.shape[0]))
 
@@ -480,6 +481,22 @@ class Context:
         b2, m1, m2 = _u8(bottom2), _u8(mask), _u8(mask2)
         assert b2.shape == m1.shape == m2.shape and b2.shape[2] == 3
         self._ck(lib().s360_frame_upload_pole_removal(self.h, _p(b2), _p(m1), _p(m2), b2.shape[1], b2.shape[0]))
+
+    def upload_bottom2(self, bottom2):
+        """s360_frame_upload_bottom2: the secondary bottom camera's image (BGR) alone; the masks are the context's (set_pole_masks)."""
+        b2 = _u8(bottom2)
+        assert b2.ndim == 3 and b2.shape[2] == 3
+        self._ck(lib().s360_frame_upload_bottom2(self.h, _p(b2), b2.shape[1], b2.shape[0]))
+
+    def set_pole_masks(self, mask=None, mask2=None):
+        """s360_set_pole_masks: the two red pole masks (BGR) as state of the context, shared by its frame slots; pole removal's alpha
+        planes are computed once. No arguments: the masks are cleared."""
+        if mask is None and mask2 is None:
+            self._ck(lib().s360_set_pole_masks(self.h, None, None, 0, 0))
+            return
+        m1, m2 = _u8(mask), _u8(mask2)
+        assert m1.shape == m2.shape and m1.ndim == 3 and m1.shape[2] == 3
+        self._ck(lib().s360_set_pole_masks(self.h, _p(m1), _p(m2), m1.shape[1], m1.shape[0]))
 
     # ---- frame slots: several independent frames through one launch sequence ----
     def set_frame_slots(self, n):
@@ -762,7 +779,8 @@ class Context:
 
     def upload_frame_png(self, cameras, files):
         """s360_frame_upload_png: camera images from their banded PNG files (bytes; colour type 2, 8- or 16-bit), decoded on the
-        device straight into the frame's source slots. cameras: side indices, -1 (top), -2 (bottom). Synchronous."""
+        device straight into the frame's source slots. cameras: side indices, -1 (top), -2 (bottom), -3 (S360_CAMERA_BOTTOM2 with
+        enable_pole_removal). Synchronous."""
         k = len(cameras)
         assert k == len(files) and k > 0
         bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
@@ -793,13 +811,16 @@ class Context:
 
     def upload_jpeg(self, cameras, files):
         """s360_frame_upload_jpeg: camera images from their baseline JPEG files (bytes), decoded on the device straight into the
-        frame's source slots. cameras: side indices, -1 (top), -2 (bottom). Synchronous."""
+        frame's source slots. cameras: side indices, -1 (top), -2 (bottom), -3 (S360_CAMERA_BOTTOM2 with enable_pole_removal).
+        Synchronous."""
         k = len(cameras)
         assert k == len(files) and k > 0
         bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
         self._ck(lib().s360_frame_upload_jpeg(
             self.h, k, (C.c_int * k)(*[int(v) for v in cameras]), (C.c_void_p * k)(*[b.ctypes.data if b.size else None for b in bufs]),
             (C.c_size_t * k)(*[b.size for b in bufs])))
+
+    upload_frame_jpeg = upload_jpeg  # an alias beside upload_frame_png; upload_jpeg is the method's name
 
     def jpeg_decode_stats(self):
         """s360_jpeg_decode_stats of the last JPEG decode call on this context: a dict with files, subsequences, rounds (the
